@@ -13,6 +13,12 @@ Multi-GPU: one process per GPU (torchrun); each rank owns a contiguous shard of 
 stream (weak scaling, no data-path collective: CPIs are independent); the only collectives
 are the timing barrier and the max-over-ranks of the elapsed time.
 
+A plain run sets up, warms up, times --steps steps and prints the result line.  --full adds
+the secondary figures, each from a run of its own after the timed region: the CPU baseline,
+the single-lane per-kernel pass behind roofline.kernels and (with --host-path) the
+PCIe-inclusive host entry point.  --dump-outputs DIR writes what the last timed step computed
+as DIR/<name>.npy (seeded inputs: the same arguments give the same inputs in every run).
+
 Prints ONE JSON line (rank 0).  See DESIGN.md for the roofline accounting.
 """
 import argparse
@@ -31,6 +37,8 @@ HBM_PEAK_GBPS = 8000.0
 # BASELINE.json configs.  mode "window": batch = frame pairs per GPU per step,
 # each giving `win` windowed CPIs (MTD/main_produce_dataset_win_xzr_v2.m:94-144).
 WARMUP_S = 0.3   # default warmup: seconds of device work before the timed region
+DUMP_BYTES = 48 << 20   # --dump-outputs: bytes written in all (shared evenly by the arrays)
+DUMP_SEED = 20240607    # --dump-outputs: seed of the element sample of a large output
 
 CONFIGS = {
     "c2": dict(P=128, R=4096, batch=256, cfar=False, half=False, win=0),
@@ -63,7 +71,7 @@ def parse():
     ap.add_argument("--half", action="store_true", help="fp16 I/Q input")
     ap.add_argument("--chunk", type=int, default=0)
     ap.add_argument("--host-path", action="store_true",
-                    help="also time the PCIe-inclusive host entry point (rsp_pc_mtd_cfar, C128 column-major "
+                    help="--full: also time the PCIe-inclusive host entry point (rsp_pc_mtd_cfar, C128 column-major "
                          "host echo as MATLAB holds it, RDM + flags back to host)")
     ap.add_argument("--host-batch", type=int, default=1,
                     help="--host-path: CPIs per host call besides 32 (MATLAB calls one CPI per call)")
@@ -73,12 +81,20 @@ def parse():
     ap.add_argument("--prefilter", action="store_true",
                     help="fused iSTC (a synthetic stc curve) + MTI lag 30 in the chain (rsp_set_prefilter)")
     ap.add_argument("--streams", type=int, default=0, help="chunk pipelines (0 = library default)")
-    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="CPU baseline budget (0 = skip)")
-    ap.add_argument("--no-profile", action="store_true", help="no per-kernel HIP events in the timed region")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline figure: the CPU baseline (--cpu-seconds), the single-lane "
+                         "per-kernel pass (--lane-steps) and, when asked for, --host-path; a run without "
+                         "--full sets up, warms up, times the steps and prints the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last step computed (rank 0's shard) as "
+                         "DIR/<name>.npy, float32 or float64; an output larger than its share of %d MB is "
+                         "cut to a fixed, seeded sample of its elements" % (DUMP_BYTES >> 20))
+    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="--full: CPU baseline budget (0 = skip)")
+    ap.add_argument("--no-profile", action="store_true", help="--full: skip the single-lane per-kernel pass")
     ap.add_argument("--profile-every", type=int, default=7,
                     help="(unused; kept for old command lines)")
     ap.add_argument("--lane-steps", type=int, default=2,
-                    help="steps of the single-lane per-kernel pass after the timed region (0 = skip)")
+                    help="--full: steps of the single-lane per-kernel pass after the timed region (0 = skip)")
     ap.add_argument("--dry-run", action="store_true",
                     help="no GPU: gloo collectives, a stub step; checks the rank launcher, shards and halo")
     ap.add_argument("--share-device", action="store_true",
@@ -97,6 +113,9 @@ def parse():
     args.no_cfar = args.no_cfar or not cfg["cfar"]
     args.half = args.half or cfg["half"]
     args.win = cfg["win"]
+    if not args.full:
+        # a plain run measures the headline figure only
+        args.cpu_seconds, args.lane_steps, args.host_path = 0.0, 0, False
     return args
 
 
@@ -228,6 +247,33 @@ def cpu_baseline(spec, cfar, seconds, unit="CPI/s"):
             "host": cpus}
 
 
+def dump_outputs(path, arrays):
+    """--dump-outputs: write each device tensor of `arrays` (name -> tensor) as path/<name>.npy.
+    Complex tensors are written as [..., 2] real/imag pairs; float64 stays float64, integer
+    tensors become float64 when float32 cannot hold their values exactly (more than 24 bits),
+    everything else float32.  A tensor larger than its share of DUMP_BYTES is cut to a sample
+    of its flattened elements: sorted indices drawn (with replacement) by numpy's PCG64 seeded
+    with DUMP_SEED, the same for every run of the same shape."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BYTES // max(len(arrays), 1)
+    for name, t in arrays.items():
+        if t.is_complex():
+            t = torch.view_as_real(t)
+        wide = t.dtype == torch.float64 or (not t.dtype.is_floating_point and t.element_size() > 2)
+        flat = t.reshape(-1)
+        keep = share // (8 if wide else 4)
+        if flat.numel() > keep:
+            rng = np.random.Generator(np.random.PCG64(DUMP_SEED))
+            idx = np.sort(rng.integers(0, flat.numel(), size=keep))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        else:
+            flat = flat.reshape(t.shape)
+        np.save(os.path.join(path, name + ".npy"),
+                flat.to(torch.float64 if wide else torch.float32).cpu().numpy())
+
+
 def hbm_ceiling():
     """The measured streaming ceiling of this part (profiles/hbm_ceiling.json, written from
     tools/micro/hbm_ceiling.hip): copy (equal read and write bytes, the chain's mix), read-only,
@@ -300,6 +346,8 @@ def bench_ingest(args, world, rank, local, dev, dist):
     gpu_ms = ev0.elapsed_time(ev1)
     if world > 1:
         elapsed = shard.max_over_ranks(elapsed, dist, device=dev)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"beams": out})
     cpu = None
     if rank == 0 and args.cpu_seconds > 0:
         # the fp64 oracle restatement of FrameDataRead_xzr.m on one host thread
@@ -392,6 +440,8 @@ def bench_prefilter(args, world, rank, local, dev, dist):
     elapsed, gpu_ms = _timed(args, world, dev, dist, stream, step)
     if world > 1:
         elapsed = shard.max_over_ranks(elapsed, dist, device=dev)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"filtered": out})
     cpu = None
     if rank == 0 and args.cpu_seconds > 0:
         sys.path.insert(0, os.path.join(ROOT, "oracle"))
@@ -492,6 +542,12 @@ def bench_measure(args, world, rank, local, dev, dist):
     gpu_ms = ev0.elapsed_time(ev1)
     if world > 1:
         elapsed = shard.max_over_ranks(elapsed, dist, device=dev)
+    if rank == 0 and args.dump_outputs:
+        # rows past a CPI's hit count are never written: dump them as zeros
+        live = (torch.arange(max_hits, device=dev)[None, :] < count[:, :1])[..., None]
+        dump_outputs(args.dump_outputs, {"est": torch.where(live, est, torch.zeros_like(est)),
+                                         "cells": torch.where(live, cells, torch.zeros_like(cells)),
+                                         "count": count})
     cpu = None
     if rank == 0 and args.cpu_seconds > 0:
         sys.path.insert(0, os.path.join(ROOT, "oracle"))
@@ -837,6 +893,8 @@ def main():
     if world > 1:
         plans = [None] * world
         dist.all_gather_object(plans, plan)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"rdm": rdm, "flag": flag} if cfar else {"rdm": rdm})
 
     # Per-kernel device times, measured separately from the throughput: a short pass on ONE
     # chunk pipeline (rsp_set_streams(1)) with every launch bracketed by HIP events on the

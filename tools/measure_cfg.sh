@@ -12,7 +12,7 @@ EXTRA="$*"
 OUT="$ROOT/gpurun_out/$CFG"; rm -rf "$OUT"; mkdir -p "$OUT"
 export TMPDIR=/tmp
 STEPS=${STEPS:-10}
-timeout -k 10 300 python bench.py --config $CFG --steps $STEPS --cpu-seconds ${CPU_SECONDS:-10} $EXTRA \
+timeout -k 10 300 python bench.py --full --config $CFG --steps $STEPS --cpu-seconds ${CPU_SECONDS:-10} $EXTRA \
     > "$OUT/bench.log" 2> "$OUT/bench.err" || { echo "bench rc=$?"; tail -5 "$OUT/bench.err"; exit 1; }
 tail -1 "$OUT/bench.log" | python -c "import json,sys; d=json.loads(sys.stdin.read()); r=d['roofline']; print('$CFG', d['value'], d['unit'], 'ms/step', d['ms_per_step'], 'frac', r['frac'], {k: (v['avg_us'], v.get('frac')) for k, v in r.get('kernels', {}).items()})"
 (cd /tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof" -o run -- \

@@ -1,5 +1,5 @@
-import json, glob, sys
-for f in sorted(glob.glob('gpurun_out/ablate/*.json')):
+import json, glob, os, sys
+for f in sorted(glob.glob(os.path.join(os.environ.get('OUT', 'bench_out'), 'ablate', '*.json'))):
     l = [x for x in open(f) if x.startswith('{')]
     if not l:
         print(f, 'no output'); continue
