@@ -49,13 +49,15 @@
 extern "C" {
 #endif
 
-#define RSP_ABI_VERSION 4   /* 2: rsp_set_fused / rsp_chain_check removed, rsp_set_pc_split added;
+#define RSP_ABI_VERSION 5   /* 2: rsp_set_fused / rsp_chain_check removed, rsp_set_pc_split added;
                                3: rsp_set_host_pipeline;
                                4: rsp_set_flow / rsp_flow_status (round 5's opt-in dataflow launch,
                                   with its RSP_K_FLOW profile slot) removed; rsp_set_range_concat
                                   added; rsp_profile_read_n
                                   takes the arrays' length, rsp_profile_read writes exactly the 4
-                                  ABI-3 entries */
+                                  ABI-3 entries;
+                               5: rsp_score_dev / rsp_score_summary with rsp_score_params and
+                                  rsp_score_result added */
 #define RSP_MAX_SEG 4
 #define RSP_MAX_FIR_TAPS 64
 
@@ -403,6 +405,91 @@ int rsp_motion_measure_dev(rsp_ctx* ctx, const float* d_sum, const float* d_diff
                            int64_t V, int64_t R, int64_t batch, const rsp_measure_params* mp,
                            const double* d_r_scale, const double* d_v_scale, int64_t max_hits,
                            double* d_est, int32_t* d_cells /* nullable */, int32_t* d_count, void* stream);
+
+/* ---- detection scoring against truth (main_cfar.m's evaluation functions) ---------------- */
+/* The four local functions at the end of MatlabProcess_xuzerui/CFAR_WangCai/main_cfar.m, the
+ * reason for its `for T=[5]` threshold loop (:40), over a device-resident batch of flag matrices:
+ *   fa    = fun_frame_fa(cfarFlag, R_True, V_True, R_True_index, V_True_index)        (:163-175)
+ *   drate = fun_drate(cfarFlag_all, R, V, r_axis, v_axis, frameRInds)                 (:177-206)
+ *   acc   = fun_accuracy(cfarFlag_all, R, V, r_axis, v_axis, frameRInds)              (:208-234)
+ *   pof   = fun_PCF(cfarFlag_all, R, V, r_axis, v_axis, frameRInds, MTD_data_all)     (:236-279)
+ * Every one of them reduces a whole V x R flag matrix (fun_PCF: and the RDM) to a few integers
+ * before any arithmetic.  rsp_score_dev computes those integers on the GPU, one 8-int record per
+ * CPI; rsp_score_summary turns the records into the reference's numbers on the host, in its
+ * operation order.  Only batch x 8 ints cross PCIe.
+ *
+ * d_flag: uint8 [batch][V][ld] with values 0/1 (the chain's d_flag), d_rdm: float32 of the same
+ * geometry or NULL (no fun_PCF peak search), d_truth: int32 [batch][3] = {v_idx, r_idx, valid},
+ * the truth's nearest axis bins, 0-based (MATLAB's V_True_index - 1, R_True_index - 1; :183-184
+ * take the first bin of a tie), and whether the truth passes the gate
+ * abs(V)>3 && abs(V)<20 && R>400 && R<2000 (:165, :186, :217, :246).  With sp->ld > R (and
+ * sp->cpi_stride) the matrices are row / column windows of larger planes -- clip.m:12's rows
+ * 691:845 of a 1536-row RDM are a pointer offset, not a copy.
+ *
+ * d_rec: int32 [batch][8] per CPI (fields 1..7 are 0 for a truth that is not valid):
+ *   [0] n_flags     sum of all V x R flags
+ *   [1] n_box       flags in rows v_idx-hv..v_idx+hv, columns r_idx-hr..r_idx+hr (:167, :188, :219),
+ *                   the box clipped to the matrix
+ *   [2] box_status  bit 0: the box leaves the matrix on the low side (an index error in all four
+ *                   functions); bit 1: on the high side (an index error for the reads of
+ *                   fun_drate / fun_accuracy; fun_frame_fa's assignment there grows its copy,
+ *                   whose sum is unchanged, while m, n were taken before: no error)
+ *   [3] n_pcf       flags in fun_PCF's box: +-n_cell around the truth after the if / elseif chain
+ *                   of :248-258, which clips at most ONE side (the first that applies of: rows
+ *                   below 1, rows above v_lim, columns below 1, columns above r_lim); 0 when that
+ *                   box is an index error
+ *   [4] pcf_status  bit 0: a non-empty range of that box still leaves the matrix (MATLAB stops)
+ *   [5] n_peak      cells of the WHOLE matrix equal to the maximum of the RDM over the box
+ *                   ([v_ind, r_ind] = find(local_max == MTD_data), :262, searches everything);
+ *                   computed when n_pcf > 0 and d_rdm != NULL, otherwise 0.  NaN cells never match.
+ *   [6] peak_v, [7] peak_r   0-based cell of the first match in find() order (smallest r*V + v)
+ * Two or more matches make dv a vector and dv^2 a MATLAB error (:265): n_peak tells.
+ * The records are combined from per-workgroup partial results with integer adds and an integer
+ * minimum only, so they do not depend on scheduling.
+ *
+ * Quirks of the reference that are kept, not fixed:
+ *   - `for i=1:length(cfarFlag_all)` (:179, :210, :238) is the LARGEST dimension of the 3-D array,
+ *     the frame count only when there are more frames than rows and columns.  Here the loop
+ *     runs over the batch.
+ *   - fun_accuracy counts a frame without a valid truth when it holds ANY flag (:224-227).
+ * Works on any context, the CFAR-only kind included; needs no per-context scratch (the partial
+ * results accumulate in d_rec itself). */
+typedef struct {
+    int32_t hv, hr;          /* half height / width of the detection box (3, 7) */
+    int32_t n_cell;          /* fun_PCF's n_cell (20) */
+    int32_t v_lim, r_lim;    /* the limits fun_PCF's elseif chain compares with (155, 288: the
+                                clipped dataset's size, hard-coded at :250-255); not assumed to be V, R */
+    int32_t reserved;        /* 0 */
+    int64_t ld;              /* row pitch of the planes in elements (0 = R) */
+    int64_t cpi_stride;      /* elements between CPIs (0 = V * ld) */
+} rsp_score_params;
+
+enum { RSP_SCORE_FA = 0, RSP_SCORE_DRATE = 1, RSP_SCORE_ACC = 2, RSP_SCORE_PCF = 3 };
+
+typedef struct {
+    double drate;              /* fun_drate: #(t>0) / #(valid); 0/0 = NaN as in MATLAB */
+    double acc;                /* fun_accuracy: count / batch */
+    double pof;                /* fun_PCF: mean of the scored frames' pof; NaN when none scored */
+    int64_t n_valid;           /* truths that pass the gate */
+    int64_t n_scored;          /* frames in fun_PCF's pof_list */
+    int64_t n_index_error[4];  /* CPIs at which the reference stops with an index error, by
+                                  function (RSP_SCORE_*); they contribute nothing to that
+                                  function's number (fa[i] = NaN) */
+    int64_t n_multi_peak;      /* valid CPIs with n_peak > 1: fun_PCF stops at dv^2; left out of pof */
+} rsp_score_result;
+
+/* Asynchronous on `stream`. */
+int rsp_score_dev(rsp_ctx* ctx, const uint8_t* d_flag, const float* d_rdm /* nullable */, int64_t V,
+                  int64_t R, int64_t batch, const rsp_score_params* sp, const int32_t* d_truth,
+                  int32_t* d_rec, void* stream);
+/* Host only (no GPU, no context): rec / truth are host copies of d_rec / d_truth.  fa[i]
+ * (nullable) = fun_frame_fa of CPI i; out = the batch's fun_drate, fun_accuracy, fun_PCF
+ * (dv_base = 1/0.2719, dr_base = 30/6; pof = 1 - l/l_base below l_base, exp(1 - l/l_base) - 1
+ * from there, :264-271) and the counters.  A CPI with n_pcf > 0 and n_peak == 0 (no RDM was
+ * given) is not scored.  Returns RSP_ERR_ARG for a NULL rec / truth / sp / out. */
+int rsp_score_summary(const int32_t* rec, const int32_t* truth, int64_t batch, int64_t V, int64_t R,
+                      const rsp_score_params* sp, double* fa /* [batch], nullable */,
+                      rsp_score_result* out);
 
 /* ---- echo pre-filters ---------------------------------------------------- */
 /* iSTC and MTI on a device-resident echo batch, complex64 [batch][P][R] (row = pulse, the

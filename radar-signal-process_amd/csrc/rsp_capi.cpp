@@ -301,7 +301,7 @@ static void zero_v_band(int64_t rows, int div, int* lo, int* hi) {
 }
 
 // ------------------------------------------------------------------ public API
-const char* rsp_version(void) { return "rsp-mi355x 0.5.0 (gfx950, abi 4)"; }
+const char* rsp_version(void) { return "rsp-mi355x 0.5.0 (gfx950, abi 5)"; }
 
 const char* rsp_last_error(const rsp_ctx* ctx) { return ctx ? ctx->err.c_str() : g_err.c_str(); }
 
@@ -1412,6 +1412,106 @@ int rsp_motion_measure_dev(rsp_ctx* ctx, const float* d_sum, const float* d_diff
                                      max_hits, d_est, d_cells, d_count, (int32_t*)ctx->meas_band.p, nb,
                                      (hipStream_t)stream));
     return scratch_release(ctx, (hipStream_t)stream);
+}
+
+// ------------------------------------------------------------------ detection scoring
+static const char* score_params_bad(const rsp_score_params* sp) {
+    constexpr int32_t kMax = 1 << 24;
+    if (sp->hv < 0 || sp->hr < 0 || sp->n_cell < 0 || sp->hv > kMax || sp->hr > kMax || sp->n_cell > kMax)
+        return "box half sizes outside 0..2^24";
+    if (sp->v_lim < 0 || sp->r_lim < 0) return "negative v_lim / r_lim";
+    if (sp->ld < 0 || sp->cpi_stride < 0) return "negative pitch";
+    return nullptr;
+}
+
+int rsp_score_dev(rsp_ctx* ctx, const uint8_t* d_flag, const float* d_rdm, int64_t V, int64_t R, int64_t batch,
+                  const rsp_score_params* sp, const int32_t* d_truth, int32_t* d_rec, void* stream) {
+    if (!ctx) return fail(nullptr, RSP_ERR_ARG, "rsp_score_dev: null ctx");
+    if (!sp || !d_flag || !d_truth || !d_rec || batch < 0) return fail(ctx, RSP_ERR_ARG, "rsp_score_dev: bad argument");
+    if (const char* why = score_params_bad(sp)) return fail(ctx, RSP_ERR_ARG, "rsp_score_dev: %s", why);
+    // V * R below 2^31: the flag total and the packed peak index r*V + v are int32
+    if (V < 1 || R < 1 || V > (1 << 20) || R > (1 << 20) || V * R >= (int64_t)1 << 31 || batch > 0x7fffffff)
+        return fail(ctx, RSP_ERR_ARG, "rsp_score_dev: bad shape %lld x %lld x %lld", (long long)batch, (long long)V,
+                    (long long)R);
+    const int64_t ld = sp->ld ? sp->ld : R, cs = sp->cpi_stride ? sp->cpi_stride : V * ld;
+    if (ld < R || cs < (V - 1) * ld + R)
+        return fail(ctx, RSP_ERR_ARG, "rsp_score_dev: row pitch %lld / CPI stride %lld too small for %lld x %lld",
+                    (long long)ld, (long long)cs, (long long)V, (long long)R);
+    if (batch == 0) return RSP_OK;
+    if (!set_device(ctx)) return fail(ctx, RSP_ERR_HIP, "hipSetDevice failed");
+    rsp::ScoreArgs a;
+    a.V = (int)V;
+    a.R = (int)R;
+    a.hv = sp->hv;
+    a.hr = sp->hr;
+    a.n_cell = sp->n_cell;
+    a.v_lim = sp->v_lim;
+    a.r_lim = sp->r_lim;
+    a.ld = ld;
+    a.cs = cs;
+    HIP_TRY(ctx, rsp::launch_score(d_flag, d_rdm, d_truth, d_rec, (int)batch, a, (hipStream_t)stream));
+    return RSP_OK;
+}
+
+// main_cfar.m:163-279 from the records, in the reference's operation order (host only).
+int rsp_score_summary(const int32_t* rec, const int32_t* truth, int64_t batch, int64_t V, int64_t R,
+                      const rsp_score_params* sp, double* fa, rsp_score_result* out) {
+    if (!rec || !truth || !sp || !out || batch < 0 || V < 1 || R < 1)
+        return fail(nullptr, RSP_ERR_ARG, "rsp_score_summary: bad argument");
+    if (const char* why = score_params_bad(sp)) return fail(nullptr, RSP_ERR_ARG, "rsp_score_summary: %s", why);
+    rsp_score_result r{};
+    const double cells = (double)V * (double)R;                       // m*n (:164)
+    const double dv_base = 1.0 / 0.2719, dr_base = 30.0 / 6.0;        // :237
+    const double l_base = dv_base * dv_base + dr_base * dr_base;      // :266
+    double d11 = 0, d01 = 0;   // fun_drate's n_p_1_1, n_p_0_1
+    double a11 = 0, a00 = 0;   // fun_accuracy's n_p_1_1, n_p_0_0
+    double pof_sum = 0;
+    for (int64_t i = 0; i < batch; ++i) {
+        const int32_t* c = rec + i * 8;
+        const int32_t* t = truth + i * 3;
+        const bool valid = t[2] != 0;
+        const bool low = c[2] & 1, high = c[2] & 2;
+        if (!valid) {
+            if (fa) fa[i] = (double)c[0] / cells;                    // :171-174
+            if (c[0] > 0) a00 += 1;                                  // :224-227
+            continue;
+        }
+        ++r.n_valid;
+        if (low) {   // an index below 1: the assignment at :167 stops too
+            ++r.n_index_error[RSP_SCORE_FA];
+            if (fa) fa[i] = NAN;
+        } else if (fa) {
+            fa[i] = (double)(c[0] - c[1]) / cells;                   // :167-169, :174
+        }
+        if (low || high) {   // the reads at :188 / :219 stop on either side
+            ++r.n_index_error[RSP_SCORE_DRATE];
+            ++r.n_index_error[RSP_SCORE_ACC];
+        } else {
+            if (c[1] > 0) {
+                d11 += 1;
+                a11 += 1;
+            } else {
+                d01 += 1;
+            }
+        }
+        if (c[4] & 1) {
+            ++r.n_index_error[RSP_SCORE_PCF];
+        } else if (c[3] > 0 && c[5] > 0) {
+            if (c[5] > 1) {
+                ++r.n_multi_peak;
+            } else {
+                const double dv = std::fabs((double)t[0] - (double)c[6]), dr = std::fabs((double)t[1] - (double)c[7]);
+                const double l = dv * dv + dr * dr;                  // :265
+                pof_sum += l < l_base ? 1.0 - l / l_base : std::exp(1.0 - l / l_base) - 1.0;   // :267-271
+                ++r.n_scored;
+            }
+        }
+    }
+    r.drate = d11 / (d11 + d01);                                     // :205 (0/0 = NaN)
+    r.acc = batch ? (a11 + a00) / (double)batch : NAN;               // :232
+    r.pof = pof_sum / (double)r.n_scored;                            // :278 (0/0 = NaN)
+    *out = r;
+    return RSP_OK;
 }
 
 // ------------------------------------------------------------------ echo pre-filters

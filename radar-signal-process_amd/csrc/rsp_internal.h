@@ -163,6 +163,16 @@ hipError_t launch_measure(const float* sum, const float* diff, const uint8_t* fl
                           const MeasureArgs& a, const double* r_scale, const double* v_scale, int64_t max_hits,
                           double* est, int32_t* cells, int32_t* count, int32_t* band_cnt, int nb, hipStream_t st);
 
+// Detection scoring (rsp_score.hip): rsp_score_params with the shape and the resolved pitches.
+struct ScoreArgs {
+    int V, R;
+    int hv, hr, n_cell, v_lim, r_lim;
+    int64_t ld, cs;   // row pitch and CPI stride of the flag / RDM planes, in elements
+};
+// rec [batch][8] int32 (rsp.h); rdm may be null (no peak search).
+hipError_t launch_score(const uint8_t* flag, const float* rdm, const int32_t* truth, int32_t* rec, int batch,
+                        const ScoreArgs& a, hipStream_t st);
+
 // Echo pre-filters (rsp_prefilter.hip): iSTC gain per range bin and/or MTI row difference.
 hipError_t launch_prefilter(const float2* in, float2* out, const float* gain, int P, int R, int64_t batch, int lag,
                             hipStream_t st);

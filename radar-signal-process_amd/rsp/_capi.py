@@ -31,7 +31,7 @@ EXPORTS = ("rsp_version", "rsp_create", "rsp_destroy", "rsp_last_error", "rsp_se
            "rsp_create_v2", "rsp_create_legacy", "rsp_window_pc_mtd_cfar_dev", "rsp_pc_mtd_cfar_diff_dev",
            "rsp_mtd_cfar_dev", "rsp_set_pc_split", "rsp_set_host_pipeline", "rsp_ingest_record_bytes",
            "rsp_ingest_ddc_dev", "rsp_ingest_frame_dev", "rsp_motion_measure_dev", "rsp_prefilter_dev", "rsp_set_prefilter",
-           "rsp_pc_mtd_cfar_f64", "rsp_cfar_f64", "rsp_set_range_concat")
+           "rsp_pc_mtd_cfar_f64", "rsp_cfar_f64", "rsp_set_range_concat", "rsp_score_dev", "rsp_score_summary")
 RSP_NKERNELS = 4
 KERNEL_NAMES = ("pc_kernel", "mtd_kernel", "cfar_r_kernel", "cfar_v_kernel")
 
@@ -80,6 +80,19 @@ class rsp_measure_params(C.Structure):
                 ("ele_comp", C.c_double), ("ele_sys_err", C.c_double), ("ld", C.c_int64),
                 ("cpi_stride", C.c_int64)]
 
+
+class rsp_score_params(C.Structure):
+    _fields_ = [("hv", C.c_int32), ("hr", C.c_int32), ("n_cell", C.c_int32), ("v_lim", C.c_int32),
+                ("r_lim", C.c_int32), ("reserved", C.c_int32), ("ld", C.c_int64), ("cpi_stride", C.c_int64)]
+
+
+class rsp_score_result(C.Structure):
+    _fields_ = [("drate", C.c_double), ("acc", C.c_double), ("pof", C.c_double), ("n_valid", C.c_int64),
+                ("n_scored", C.c_int64), ("n_index_error", C.c_int64 * 4), ("n_multi_peak", C.c_int64)]
+
+
+# rsp_score_result.n_index_error slots
+RSP_SCORE_FA, RSP_SCORE_DRATE, RSP_SCORE_ACC, RSP_SCORE_PCF = range(4)
 
 # per-PRT ingest status codes (rsp_ingest_ddc_dev)
 (RSP_PRT_OK, RSP_PRT_TRUNCATED, RSP_PRT_TAIL_TRUNCATED, RSP_PRT_BAD_COUNT, RSP_PRT_BAD_SHAPE,
@@ -157,6 +170,11 @@ def load_library(path=None):
     lib.rsp_motion_measure_dev.restype = C.c_int
     lib.rsp_motion_measure_dev.argtypes = [vp, vp, vp, vp, i64, i64, i64, C.POINTER(rsp_measure_params), vp, vp,
                                            i64, vp, vp, vp, vp]
+    lib.rsp_score_dev.restype = C.c_int
+    lib.rsp_score_dev.argtypes = [vp, vp, vp, i64, i64, i64, C.POINTER(rsp_score_params), vp, vp, vp]
+    lib.rsp_score_summary.restype = C.c_int
+    lib.rsp_score_summary.argtypes = [vp, vp, i64, i64, i64, C.POINTER(rsp_score_params), vp,
+                                      C.POINTER(rsp_score_result)]
     lib.rsp_prefilter_dev.restype = C.c_int
     lib.rsp_prefilter_dev.argtypes = [vp, vp, vp, i64, i64, i64, vp, i32, vp]
     lib.rsp_profile.restype = C.c_int
