@@ -188,6 +188,17 @@ const char* rsp_last_error(const rsp_ctx* ctx);
  * launches beat Infinity-Cache residency for the window stream). */
 int rsp_set_chunk(rsp_ctx* ctx, int64_t cpis_per_chunk);
 
+/* Per-pipeline chunk sizes (an addition within ABI 5).  Chunk k of a chain call runs on pipeline
+ * k % n; with this call pipeline i's chunks are cpis[i] CPIs each, so the batch is cut cpis[0],
+ * cpis[1], ..., cpis[n-1], cpis[0], ... and only the final chunk is short.  Pipelines of unequal
+ * chunks have unequal periods, so their PC / MTD phases cannot lock.  1 <= n <= 4 sets both the
+ * sizes and the pipeline count of non-window chains (as rsp_set_streams(n) would); n = 0 restores
+ * the default.  A later rsp_set_chunk with a size > 0 means equal chunks again.  Window mode is
+ * unaffected.  Results do not depend on the chunking.  Per-pipeline scratch is sized by the
+ * largest chunk: n * max(cpis) * P * R_out * 8 bytes of PC scratch, and with a range
+ * concatenation as much again times pc_width / R_out for its staging rows. */
+int rsp_set_lane_chunks(rsp_ctx* ctx, const int64_t* cpis, int32_t n);
+
 /* Number of chunk pipelines (1..4; 0 = the default: 2, window mode 1): chunk k runs on the
  * caller's stream or on one of n-1 context-owned streams that fork from and join back into
  * it, so consecutive chunks overlap.  Each pipeline owns one PC scratch slot (n = 1: every
@@ -292,6 +303,15 @@ int rsp_pc_dev(rsp_ctx* ctx, const void* d_echo, int32_t dtype, int64_t batch, v
  * enable = 0 selects the whole-length transforms.  The threshold is fixed (4096 points).
  * RSP_ERR_UNSUPPORTED on a context without the specialised PC kernels (nothing to select). */
 int rsp_set_pc_split(rsp_ctx* ctx, int32_t enable);
+
+/* Pruned pulse-compression kernels (default on; an addition within ABI 5): where a matched
+ * filter's rows end in whole 1/16-transform slices that are zero padding (input) or are cut by
+ * out_len (output), a kernel instance built for the built-in presets skips those slices' loads,
+ * stores and butterfly operations.  Every stored value is unchanged, except that an exact zero
+ * may come out with the other sign.  enable = 0 runs the generic instances (for A/B runs and
+ * tests).  Shapes without a built instance run the generic one either way.
+ * RSP_ERR_UNSUPPORTED on a context without the specialised PC kernels (nothing to select). */
+int rsp_set_pc_prune(rsp_ctx* ctx, int32_t enable);
 
 /* Range concatenation between pulse compression and the MTD, replacing
  *   Echo_0 = fun_lss_range_concate(prtNum, Echo_0)

@@ -26,6 +26,7 @@
 
 #include "../../include/rsp.h"
 #include "rsp_hostpool.h"
+#include "rsp_chunkplan.h"
 #include "rsp_internal.h"
 
 using cd = std::complex<double>;
@@ -52,6 +53,10 @@ struct rsp_ctx {
     int pc_ols_min = RSP_PC_OLS_MIN;    // overlap-save split of segments longer than this
     std::vector<rsp::PcMfArgs> pc_mf_whole, pc_mf_split;   // per MF segment, for rsp_set_pc_split
     std::vector<rsp::PcMfArgs> pc_mf;   // one launch per matched-filter segment
+    int64_t lane_cpis[rsp::kMaxLanes] = {};   // rsp_set_lane_chunks: per-pipeline chunk sizes
+    int nlane_cpis = 0;                       // 0: equal chunks / the default split
+    // rsp_set_pc_prune: pruned PC kernel instances where built (dev A/B: RSP_PC_PRUNE=0 starts off)
+    bool pc_prune = [] { const char* v = getenv("RSP_PC_PRUNE"); return !(v && *v == '0'); }();
     rsp::MtdArgs mtd{};
     int64_t V = 0;                      // Doppler rows (rsp_params.mtd_nfft or P)
     int beams = 1;                      // 2: DMX left/right pair
@@ -270,6 +275,20 @@ static int pc_overlap_save(rsp_ctx* ctx, const rsp_pc_segment& g, rsp::PcMfArgs&
     a.nsub = best_n;
     a.sub_step = best_step;
     return RSP_OK;
+}
+
+// PcMfArgs::zin / zout of a segment (after the overlap-save decision): whole slices of
+// G = nfft/16 points past the longest input / output window of any sub-block.
+static void pc_prune_counts(rsp::PcMfArgs& a) {
+    a.zin = a.zout = 0;
+    const int n = a.mf.nfft, g = n / 16;
+    if (g < 64 || g % 64) return;   // only wave-uniform rows range-check by buffer resource
+    int in = a.mf.in_len, out = a.mf.out_len;
+    if (a.nsub > 1) out = out < a.sub_step ? out : a.sub_step;   // (sub-block 0 has the longest windows)
+    in = in < 0 ? 0 : in < n ? in : n;
+    out = out < 0 ? 0 : out < n ? out : n;
+    a.zin = (n - in) / g;
+    a.zout = (n - out) / g;
 }
 
 static int ensure(rsp_ctx* ctx, DevBuf& b, size_t bytes) {
@@ -531,11 +550,13 @@ int rsp_create(rsp_ctx** out, int device, const rsp_params* prm) {
             } else if (!rsp::pc_mf_supported(a.mf.nfft, 0)) {
                 ok = false;
             }
+            pc_prune_counts(a);
             ctx->pc_mf_whole.push_back(a);
             if (ok) {
                 const int rc = pc_overlap_save(ctx, p.seg[s], a);
                 if (rc) return bail(rc);
             }
+            pc_prune_counts(a);
             ctx->pc_mf_split.push_back(a);
             ctx->pc_mf.push_back(a);
         }
@@ -734,7 +755,34 @@ int rsp_set_chunk(rsp_ctx* ctx, int64_t cpis) {
     if (!ctx) return fail(nullptr, RSP_ERR_ARG, "rsp_set_chunk: null ctx");
     if (cpis < 0) return fail(ctx, RSP_ERR_ARG, "rsp_set_chunk: negative chunk");
     ctx->chunk = cpis;
+    if (cpis > 0) ctx->nlane_cpis = 0;   // an explicit chunk means equal chunks
     return RSP_OK;
+}
+
+int rsp_set_lane_chunks(rsp_ctx* ctx, const int64_t* cpis, int32_t n) {
+    if (!ctx) return fail(nullptr, RSP_ERR_ARG, "rsp_set_lane_chunks: null ctx");
+    if (n < 0 || n > rsp::kMaxLanes || (n > 0 && !cpis))
+        return fail(ctx, RSP_ERR_ARG, "rsp_set_lane_chunks: n must be 0..%d with a size list", rsp::kMaxLanes);
+    for (int i = 0; i < n; ++i)
+        if (cpis[i] < 1) return fail(ctx, RSP_ERR_ARG, "rsp_set_lane_chunks: chunk %d is %lld CPIs", i, (long long)cpis[i]);
+    for (int i = 0; i < n; ++i) ctx->lane_cpis[i] = cpis[i];
+    ctx->nlane_cpis = n;
+    return RSP_OK;
+}
+
+// The default two-lane split of an unset chunk of cu CPIs (run_chain_body): *a == *b keeps the
+// equal chunks.  Dev A/B: RSP_LANE_SPLIT="a,b" in CPIs (read once), "0" for equal chunks.
+static void default_lane_split(int64_t cu, int64_t* a, int64_t* b) {
+    static const struct Env { int64_t a = -1, b = -1; Env() {
+        const char* v = getenv("RSP_LANE_SPLIT");
+        if (v && *v) { long long x = 0, y = 0; const int k = sscanf(v, "%lld,%lld", &x, &y); a = x; b = k == 2 ? y : x; }
+    } } env;
+    if (env.a >= 0) {
+        *a = env.a;
+        *b = env.b;
+        return;
+    }
+    *a = *b = cu;   // (no unequal pair beat the equal chunks at c3: DESIGN.md §7e)
 }
 
 
@@ -840,7 +888,7 @@ static int scratch_release(rsp_ctx* ctx, hipStream_t s) {
 }
 
 static hipError_t run_pc(rsp_ctx* ctx, const void* ein, int dtype, float2* out, int64_t rows, hipStream_t s,
-                         int slot = 0);
+                         int slot, int64_t slot_rows);
 
 // Run one kernel launch, bracketed by HIP events on `s` when profiling is on (every
 // ctx->prof-th launch: a timing event costs the stream a few microseconds, so a sampled
@@ -868,11 +916,13 @@ static hipError_t timed(rsp_ctx* ctx, int k, hipStream_t s, F&& launch) {
 static hipError_t run_pc_rows(rsp_ctx* ctx, const void* ein, int dtype, float2* out, int64_t rows, hipStream_t s);
 // Pulse compression of `rows` echo rows into `out` ([rows][R_out]).  With a range concatenation
 // (rsp_set_range_concat) the full-width PC rows land in cat_tmp slot `slot` (ensured by the caller:
-// slot * rows * pc_w complex per slot) and the parts are gathered into `out` by 2-D copies on s.
+// slot_rows * pc_w complex per slot, slot_rows >= rows) and the parts are gathered into `out` by
+// 2-D copies on s.  The slot starts at its fixed capacity, not at this call's row count: a short
+// last chunk on lane 1 would otherwise start inside lane 0's slot while lane 0 still uses it.
 static hipError_t run_pc(rsp_ctx* ctx, const void* ein, int dtype, float2* out, int64_t rows, hipStream_t s,
-                         int slot) {
+                         int slot, int64_t slot_rows) {
     if (ctx->ncat == 0) return run_pc_rows(ctx, ein, dtype, out, rows, s);
-    float2* full = (float2*)ctx->cat_tmp.p + (size_t)slot * rows * ctx->pc_w;
+    float2* full = (float2*)ctx->cat_tmp.p + (size_t)slot * (size_t)slot_rows * ctx->pc_w;
     hipError_t e = run_pc_rows(ctx, ein, dtype, full, rows, s);
     if (e != hipSuccess) return e;
     const size_t so = sizeof(float2);
@@ -919,11 +969,13 @@ static hipError_t run_pc_rows(rsp_ctx* ctx, const void* ein, int dtype, float2* 
     if (ctx->pc_mf.size() == 2 && rsp::pc_pair_supported(ctx->pc_mf[0].mf.nfft, ctx->pc_mf[1].mf.nfft)) {
         rsp::PcMfArgs a1 = ctx->pc_mf[0], a2 = ctx->pc_mf[1];
         a1.rows = a2.rows = (int)rows;
+        if (!ctx->pc_prune) a1.zin = a1.zout = a2.zin = a2.zout = 0;
         return timed(ctx, RSP_K_PC, s, [&] { return rsp::launch_pc_mf(ein, dtype, out, a1, &a2, s); });
     }
     for (const rsp::PcMfArgs& a0 : ctx->pc_mf) {
         rsp::PcMfArgs a = a0;
         a.rows = (int)rows;
+        if (!ctx->pc_prune) a.zin = a.zout = 0;
         hipError_t e = timed(ctx, RSP_K_PC, s, [&] { return rsp::launch_pc_mf(ein, dtype, out, a, nullptr, s); });
         if (e != hipSuccess) return e;
     }
@@ -973,7 +1025,7 @@ int rsp_pc_dev(rsp_ctx* ctx, const void* d_echo, int32_t dtype, int64_t batch, v
     if (dtype != RSP_C64 && dtype != RSP_C32F16) return fail(ctx, RSP_ERR_ARG, "rsp_pc_dev: dtype %d", dtype);
     if (!set_device(ctx)) return fail(ctx, RSP_ERR_HIP, "hipSetDevice failed");
     if (ctx->ncat == 0) {
-        HIP_TRY(ctx, run_pc(ctx, d_echo, dtype, (float2*)d_pc, batch * ctx->p.P, (hipStream_t)stream));
+        HIP_TRY(ctx, run_pc(ctx, d_echo, dtype, (float2*)d_pc, batch * ctx->p.P, (hipStream_t)stream, 0, 0));
         return RSP_OK;
     }
     // the concatenation stages full-width rows in the context's scratch
@@ -981,7 +1033,7 @@ int rsp_pc_dev(rsp_ctx* ctx, const void* d_echo, int32_t dtype, int64_t batch, v
     int rc = scratch_acquire(ctx, s);
     if (rc) return rc;
     if ((rc = cat_ensure(ctx, 1, batch * ctx->p.P))) return rc;
-    HIP_TRY(ctx, run_pc(ctx, d_echo, dtype, (float2*)d_pc, batch * ctx->p.P, s));
+    HIP_TRY(ctx, run_pc(ctx, d_echo, dtype, (float2*)d_pc, batch * ctx->p.P, s, 0, batch * ctx->p.P));
     return scratch_release(ctx, s);
 }
 
@@ -996,6 +1048,15 @@ int rsp_set_pc_split(rsp_ctx* ctx, int32_t enable) {
         ctx->pc_mf[i] = src[i];
         ctx->pc_mf[i].gain = gain;
     }
+    return RSP_OK;
+}
+
+int rsp_set_pc_prune(rsp_ctx* ctx, int32_t enable) {
+    if (!ctx) return fail(nullptr, RSP_ERR_ARG, "rsp_set_pc_prune: null ctx");
+    if (ctx->cfar_only) return fail(ctx, RSP_ERR_ARG, "rsp_set_pc_prune: CFAR-only context");
+    if (!ctx->pc_v2)   // the generic PC path has no pruned instances
+        return fail(ctx, RSP_ERR_UNSUPPORTED, "rsp_set_pc_prune: this context has no specialised PC path");
+    ctx->pc_prune = enable != 0;
     return RSP_OK;
 }
 
@@ -1081,43 +1142,74 @@ static int run_chain_body(rsp_ctx* ctx, const void* d_echo, int32_t dtype, int64
         }
     }
     if (cu > units) cu = units;
-    // Chunk boundaries: chunk k covers units [cstart[k], cstart[k + 1]), cu units each but the last.
-    std::vector<int64_t> cstart{0};
-    while (cstart.back() < units) cstart.push_back(cstart.back() + cu < units ? cstart.back() + cu : units);
-    const int64_t nchunks = (int64_t)cstart.size() - 1;
-    const int ns = (int)(nsd < nchunks ? nsd : nchunks);
+    // Chunk boundaries (rsp_chunkplan.h): chunk k covers units [cstart[k], cstart[k + 1]) on lane
+    // k % ns; a lane's chunks are lcu[lane] units each, only the call's final chunk is short.
+    // Equal chunks of cu units, unless rsp_set_lane_chunks gave the lanes their own sizes (which
+    // also sets the lane count) or the default two-lane split applies (kLaneSplit*).
+    int64_t lcu[rsp::kMaxLanes] = {cu, cu, cu, cu};
+    int nlanes = nsd;
+    if (win == 0 && ctx->nlane_cpis > 0) {
+        nlanes = ctx->nlane_cpis;
+        for (int i = 0; i < nlanes; ++i) lcu[i] = ctx->lane_cpis[i] < 65535 ? ctx->lane_cpis[i] : 65535;
+    } else if (win == 0 && ctx->chunk <= 0 && nsd == 2) {
+        int64_t a = 0, b = 0;
+        default_lane_split(cu, &a, &b);
+        if (rsp::lane_split_applies(units, a, b)) {
+            lcu[0] = a;
+            lcu[1] = b;
+        }
+    }
+    const rsp::ChunkPlan plan = rsp::plan_chunks(units, lcu, nlanes);
+    const std::vector<int64_t>& cstart = plan.cstart;
+    const int64_t nchunks = plan.nchunks();
+    const int ns = plan.ns;
     const size_t plane = (size_t)V * Ro;                  // output cells per CPI
-    const size_t cells = (size_t)cu * ocpi * plane;       // output cells per chunk slot
-    const size_t pcrows = (size_t)(cu + (win > 0 ? 1 : 0)) * NB * P;
-    int rc = pc_input ? RSP_OK : ensure(ctx, ctx->scratch_pc, (size_t)ns * pcrows * Ro * sizeof(float2));
+    // concat staging and internal RDM slots are sized by the call's largest chunk; a lane's PC
+    // scratch slot by the lane's own (16 / 24 CPIs at c3: 160 MiB of scratch, not 192)
+    const size_t cells = (size_t)plan.cap_max * ocpi * plane;       // output cells per chunk slot
+    const size_t pcrows = (size_t)(plan.cap_max + (win > 0 ? 1 : 0)) * NB * P;
+    size_t pcoff[rsp::kMaxLanes + 1] = {};   // first PC scratch row of each lane's slot
+    for (int l = 0; l < ns; ++l) pcoff[l + 1] = pcoff[l] + (size_t)(plan.cap[l] + (win > 0 ? 1 : 0)) * NB * P;
+    int rc = pc_input ? RSP_OK : ensure(ctx, ctx->scratch_pc, pcoff[ns] * Ro * sizeof(float2));
     if (rc) return rc;
     if (!pc_input && (rc = cat_ensure(ctx, ns, (int64_t)pcrows))) return rc;
-    int nreg = 0, reg = 0;
+    // hit-list regions of a lane's full chunk (nreg[lane], each `reg` indices: the region is one MTD
+    // workgroup's cells, whatever the chunk size), and all lanes' together
+    int nreg[rsp::kMaxLanes] = {}, reg = 0;
+    size_t nreg_all = 0;
     if (cfar) {
         // fused range stage: per-lane hit lists, one region per MTD workgroup sized to its
         // cells (no overflow, no global atomics), and per-workgroup counts
         if (cells > 0xffffffffull) return fail(ctx, RSP_ERR_UNSUPPORTED, "chunk too large for 32-bit hit indices");
         // two slots per lane: chunk k's list is read by the next MTD launch on its lane while
         // that launch fills the other slot
-        rsp::mtd_regions((int)V, (int)Ro, (int)(cu * ocpi), &nreg, &reg, (int)NB);
+        for (int l = 0; l < ns; ++l) {
+            rsp::mtd_regions((int)V, (int)Ro, (int)(plan.cap[l] * ocpi), &nreg[l], &reg, (int)NB);
+            nreg_all += (size_t)nreg[l];
+        }
     }
     // grouped range stages (range_mode 2): a group's outputs must stay inside the range kernels'
     // 2 GiB buffer window, and the RDM must be the caller's (internal RDM slots are reused)
     int rgrp = range_group();
-    if (cfar && nreg > 0) {   // the groups' hit-list slots within kRangeGroupBytes
-        const uint64_t slot_bytes = (uint64_t)nreg * (uint64_t)reg * 4u;
-        const uint64_t fit = kRangeGroupBytes / ((uint64_t)ns * slot_bytes);
+    if (cfar && nreg_all > 0) {   // the groups' hit-list slots within kRangeGroupBytes
+        const uint64_t round_bytes = (uint64_t)nreg_all * (uint64_t)reg * 4u;   // one slot of every lane
+        const uint64_t fit = kRangeGroupBytes / round_bytes;
         if ((uint64_t)rgrp > fit) rgrp = fit > 0 ? (int)fit : 1;
     }
+    // a lane's group spans rgrp - 1 whole rounds over the lanes plus its own last chunk
     const bool grouped = cfar && cr.rflag && d_rdm && range_mode() == 2 && rgrp > 1 &&
-                         ((uint64_t)(rgrp - 1) * (uint64_t)ns + 1u) * (uint64_t)cells * 4u < 0x80000000ull;   // (kOob, rsp_buf.h)
+                         ((uint64_t)(rgrp - 1) * (uint64_t)plan.period * ocpi * plane + (uint64_t)cells) * 4u <
+                             0x80000000ull;   // (kOob, rsp_buf.h)
     // hit-list slots per lane: grouped, a group's range launch is stream-ordered before the next
     // group's first MTD on the lane, so the next group reuses the slots
     const int spl = grouped ? rgrp : 2;
+    // lane l's slots start behind those of the lanes before it, each lane's sized by its own regions
+    size_t hbase[rsp::kMaxLanes] = {};
+    for (int l = 1; l < ns; ++l) hbase[l] = hbase[l - 1] + (size_t)spl * nreg[l - 1];
     if (cfar) {
-        rc = ensure(ctx, ctx->hit_list, (size_t)spl * ns * nreg * reg * sizeof(uint32_t));
+        rc = ensure(ctx, ctx->hit_list, (size_t)spl * nreg_all * reg * sizeof(uint32_t));
         if (rc) return rc;
-        rc = ensure(ctx, ctx->hit_ctr, (size_t)spl * ns * nreg * sizeof(uint32_t));
+        rc = ensure(ctx, ctx->hit_ctr, (size_t)spl * nreg_all * sizeof(uint32_t));
         if (rc) return rc;
     }
     if (!d_rdm) {   // internal RDM: two slots per lane for the same reason
@@ -1170,7 +1262,8 @@ static int run_chain_body(rsp_ctx* ctx, const void* d_echo, int32_t dtype, int64
         const size_t o0 = (size_t)u0 * ocpi * plane;      // output offset
         const int lane = (int)(k % ns);
         const int64_t j = k / ns;                          // the chunk's index on its lane
-        const int slot = lane * spl + (int)(j % spl);      // double-buffered per lane (grouped: one group)
+        // first region of the chunk's hit-list slot: double-buffered per lane (grouped: one group)
+        const size_t hslot = hbase[lane] + (size_t)(j % spl) * nreg[lane];
         const int64_t jg0 = j - j % rgrp;                  // grouped: the group's first chunk on the lane
         const size_t og = grouped ? (size_t)cstart[(size_t)(lane + ns * jg0)] * ocpi * plane : o0;
         hipStream_t ls = lanes[lane];
@@ -1181,8 +1274,8 @@ static int run_chain_body(rsp_ctx* ctx, const void* d_echo, int32_t dtype, int64
         if (pc_input) {   // d_echo already holds pulse-compressed rows [units][beams][P][R_out]
             pcs = (float2*)d_echo + (size_t)u0 * NB * P * Ro;
         } else {
-            pcs = (float2*)ctx->scratch_pc.p + lane * pcrows * Ro;
-            HIP_TRY(ctx, run_pc(ctx, ein, dtype, pcs, (n + (win > 0 ? 1 : 0)) * NB * P, ls, lane));
+            pcs = (float2*)ctx->scratch_pc.p + pcoff[lane] * Ro;
+            HIP_TRY(ctx, run_pc(ctx, ein, dtype, pcs, (n + (win > 0 ? 1 : 0)) * NB * P, ls, lane, (int64_t)pcrows));
         }
         m.diff = d_diff ? d_diff + o0 : nullptr;
         m.prev_nregions = 0;
@@ -1190,8 +1283,8 @@ static int run_chain_body(rsp_ctx* ctx, const void* d_echo, int32_t dtype, int64
         if (cfar) {
             m.flag = d_flag + o0;
             m.rflag = cr.rflag;
-            m.hits = (uint32_t*)ctx->hit_list.p + (size_t)slot * nreg * reg;
-            m.hit_count = (uint32_t*)ctx->hit_ctr.p + (size_t)slot * nreg;
+            m.hits = (uint32_t*)ctx->hit_list.p + hslot * reg;
+            m.hit_count = (uint32_t*)ctx->hit_ctr.p + hslot;
             const Pending& pv = pend[lane];
             if (pv.nreg > 0 && !grouped) {
                 m.prev_rdm = pv.rdm;
@@ -1215,11 +1308,11 @@ static int run_chain_body(rsp_ctx* ctx, const void* d_echo, int32_t dtype, int64
             if (grouped) {   // the group's range stages, one launch behind its last MTD
                 const bool last = k + ns >= nchunks;
                 if (j % rgrp == rgrp - 1 || last) {
-                    const int s0 = lane * spl + (int)(jg0 % spl);
-                    const int nr = (int)(j - jg0) * nreg + pv.nreg;   // full chunks, then this one's regions
+                    const size_t s0 = hbase[lane] + (size_t)(jg0 % spl) * nreg[lane];
+                    const int nr = (int)(j - jg0) * nreg[lane] + pv.nreg;   // the lane's full chunks, then this one's regions
                     HIP_TRY(ctx, timed(ctx, RSP_K_CFAR_R, ls, [&] {
-                        return rsp::launch_cfar_hits(d_rdm + og, d_flag + og, (uint32_t*)ctx->hit_list.p + (size_t)s0 * nreg * reg,
-                                                     (uint32_t*)ctx->hit_ctr.p + (size_t)s0 * nreg, nr, pv.reg, cr, ls);
+                        return rsp::launch_cfar_hits(d_rdm + og, d_flag + og, (uint32_t*)ctx->hit_list.p + s0 * reg,
+                                                     (uint32_t*)ctx->hit_ctr.p + s0, nr, pv.reg, cr, ls);
                     }));
                 }
                 pv.nreg = 0;

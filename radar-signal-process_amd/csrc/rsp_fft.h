@@ -193,6 +193,74 @@ __device__ __forceinline__ void dft16(float2* v) {
     for (int i = 0; i < 16; ++i) v[i] = x[i];
 }
 
+// ---------------------------------------------------------------- pruned register DFTs
+// A pulse-compression row whose tail is known zero (input) or never stored (output) skips the
+// butterfly operations that only touch that tail.  Every kept operation has the operands and
+// the order of the full form, so every kept value is the same bit pattern -- with one
+// exception: a dropped `a + 0` / `a - 0` passes a = -0 through where the full form gives +0.
+// Only the sign of an exact zero can differ.
+
+// dft4 with a3 == 0 (Z3) or without the a3 output (!K3: a3 is left unspecified).
+template <bool Z3, bool K3>
+__device__ __forceinline__ void dft4_p(float2& a0, float2& a1, float2& a2, float2& a3) {
+    const float2 t0 = cadd(a0, a2), t1 = csub(a0, a2);
+    float2 t2 = a1, d = a1;   // a1 + 0, a1 - 0
+    if constexpr (!Z3) {
+        t2 = cadd(a1, a3);
+        d = csub(a1, a3);
+    }
+    a0 = cadd(t0, t2);
+    a2 = csub(t0, t2);
+    a1 = add_mj(t1, d);
+    if constexpr (K3) a3 = add_pj(t1, d);
+}
+
+template <bool K3>
+__device__ __forceinline__ void dft4_a2mj_p(float2& a0, float2& a1, float2& a2, float2& a3) {
+    const float2 t0 = add_mj(a0, a2), t1 = add_pj(a0, a2);
+    const float2 t2 = cadd(a1, a3), d = csub(a1, a3);
+    a0 = cadd(t0, t2);
+    a2 = csub(t0, t2);
+    a1 = add_mj(t1, d);
+    if constexpr (K3) a3 = add_pj(t1, d);
+}
+
+// dft16 whose trailing ZI inputs are zero (v[16 - ZI ..] is not read) and whose trailing ZO
+// outputs are not needed (left unspecified); ZI, ZO <= 4.  <0, 0> is dft16.
+template <int ZI, int ZO>
+__device__ __forceinline__ void dft16_p(float2* v) {
+    static_assert(ZI >= 0 && ZI <= 4 && ZO >= 0 && ZO <= 4, "at most one dft4 leg is pruned");
+    const float c1 = 0.92387953251128675613f, s1 = 0.38268343236508977173f;
+    const float h = 0.70710678118654752440f;
+    // input 12 + n2 is zero for n2 >= 4 - ZI
+    if constexpr (ZI > 3) dft4_p<true, true>(v[0], v[4], v[8], v[12]);
+    else dft4(v[0], v[4], v[8], v[12]);
+    if constexpr (ZI > 2) dft4_p<true, true>(v[1], v[5], v[9], v[13]);
+    else dft4(v[1], v[5], v[9], v[13]);
+    if constexpr (ZI > 1) dft4_p<true, true>(v[2], v[6], v[10], v[14]);
+    else dft4(v[2], v[6], v[10], v[14]);
+    if constexpr (ZI > 0) dft4_p<true, true>(v[3], v[7], v[11], v[15]);
+    else dft4(v[3], v[7], v[11], v[15]);
+    cmul2(v[5], v[5], make_float2(c1, -s1), v[9], v[9], make_float2(h, -h));
+    cmul2(v[13], v[13], make_float2(s1, -c1), v[6], v[6], make_float2(h, -h));
+    cmul2(v[14], v[14], make_float2(-h, -h), v[7], v[7], make_float2(s1, -c1));
+    cmul2(v[11], v[11], make_float2(-h, -h), v[15], v[15], make_float2(-c1, s1));
+    // output k1 + 12 (the a3 of leg k1) is unused for k1 >= 4 - ZO
+    dft4_p<false, (ZO < 4)>(v[0], v[1], v[2], v[3]);
+    dft4_p<false, (ZO < 3)>(v[4], v[5], v[6], v[7]);
+    dft4_a2mj_p<(ZO < 2)>(v[8], v[9], v[10], v[11]);
+    dft4_p<false, (ZO < 1)>(v[12], v[13], v[14], v[15]);
+    // leg k1 left X[k1 + 4*k2] in v[4*k1 + k2]
+    float2 x[16];
+#pragma unroll
+    for (int k1 = 0; k1 < 4; ++k1) {
+#pragma unroll
+        for (int k2 = 0; k2 < 4; ++k2) x[k1 + 4 * k2] = v[4 * k1 + k2];
+    }
+#pragma unroll
+    for (int i = 0; i < 16; ++i) v[i] = x[i];
+}
+
 template <int R>
 __device__ __forceinline__ void dft(float2* v) {
     if constexpr (R == 2) {
@@ -507,9 +575,65 @@ __device__ __forceinline__ void xsync() {
     }
 }
 
-template <int N, int G, int Ns, int E, int WO, int NW, bool WS = false>
+// Butterflies I..PER-1 of one pass.  ZI > 0 (the first pass): slices >= E - ZI of u are known
+// zero; ZO > 0 (the last pass): slices >= E - ZO of u are not needed afterwards and are left
+// unspecified.  Output r of butterfly I is slice I + r*PER.  The pruned forms exist for the
+// radix-16 single-butterfly pass (ZI, ZO <= 4) and for the a3 output of a radix-4 last pass;
+// any other plan runs the full butterflies, which is merely not faster.
+template <int R, int PER, int E, int L, int Ns, int ZI, int ZO, int I = 0>
+__device__ __forceinline__ void fft_bfly_w(float2 (&u)[E], const float2* w) {
+    if constexpr (I < PER) {
+        float2 v[R];
+#pragma unroll
+        for (int r = 0; r < R; ++r) v[r] = u[I + r * PER];
+        if constexpr (Ns > 1) tw_apply<R>(v, w + I * L);
+        if constexpr (R == 16 && PER == 1 && (ZI > 0 || ZO > 0)) {
+            dft16_p<(ZI < 4 ? ZI : 4), (ZO < 4 ? ZO : 4)>(v);
+        } else if constexpr (R == 4 && ZO > 0) {
+            dft4_p<false, (I + 3 * PER < E - ZO)>(v[0], v[1], v[2], v[3]);
+        } else {
+            dft<R>(v);
+        }
+#pragma unroll
+        for (int r = 0; r < R; ++r) u[I + r * PER] = v[r];
+        fft_bfly_w<R, PER, E, L, Ns, ZI, ZO, I + 1>(u, w);
+    }
+}
+
+// ZI: the trailing ZI slices of u are zero on entry (used by the first pass); ZO: the trailing
+// ZO slices of the result are not needed (used by the last pass).
+template <int N, int G, int Ns, int E, int WO, int NW, bool WS = false, int ZI = 0, int ZO = 0>
 __device__ __forceinline__ void fft_reg_w(float2 (&u)[E], float2* buf, int t, const float2 (&w)[NW]) {
-    if constexpr (Ns < N) {
+    if constexpr (Ns < N && (ZI > 0 || ZO > 0)) {
+        constexpr int R = pick_radix_e(N / Ns, E);
+        static_assert(R != 0, "no radix divides both the remaining length and E");
+        constexpr int NB = N / R;
+        constexpr int PER = E / R;
+        constexpr int L = tw_loads(R);
+        constexpr bool kLast = Ns * R >= N;
+        static_assert(NB == PER * G, "thread count and radix plan disagree");
+        if constexpr (Ns > 1) {
+#pragma unroll
+            for (int i = 0; i < PER; ++i) {
+                const int b = t + i * G;
+#pragma unroll
+                for (int r = 0; r < R; ++r) u[i + r * PER] = buf[slot<NB, R>(b, r)];
+            }
+        }
+        fft_bfly_w<R, PER, E, L, Ns, (Ns == 1 ? ZI : 0), (kLast ? ZO : 0)>(u, w + WO);
+        if constexpr (!kLast) {
+            xsync<WS>();  // WAR: earlier readers of buf are done
+#pragma unroll
+            for (int i = 0; i < PER; ++i) {
+                const int j = t + i * G;
+                const int base = (j / Ns) * Ns * R + (j % Ns);
+#pragma unroll
+                for (int r = 0; r < R; ++r) buf[slot<Ns, R>(base, r)] = u[i + r * PER];
+            }
+            xsync<WS>();  // RAW
+        }
+        fft_reg_w<N, G, Ns * R, E, WO + (Ns > 1 ? PER * L : 0), NW, WS, 0, ZO>(u, buf, t, w);
+    } else if constexpr (Ns < N) {
         constexpr int R = pick_radix_e(N / Ns, E);
         static_assert(R != 0, "no radix divides both the remaining length and E");
         constexpr int NB = N / R;

@@ -73,6 +73,10 @@ struct PcMfArgs {
     // outputs [j*sub_step, (j+1)*sub_step) -- sub_step = mf.nfft - replica length + 1, so no
     // output wraps.  nsub <= 1: the whole segment in one mf.nfft-point transform.
     int nsub, sub_step;
+    // Slices of G = nfft/16 points at the end of the transform that lie past in_len (zin: known
+    // zero input) / past out_len (zout: never stored) in every sub-block; 0 when the row is not
+    // wave-uniform or rsp_set_pc_prune is off.  The launcher picks a pruned kernel instance from them.
+    int zin, zout;
     const float* gain;   // fused iSTC (rsp_set_prefilter): echo column n scaled by gain[n], or null
     int nzero;
     int zero_lo[RSP_MAX_SEG + 1];

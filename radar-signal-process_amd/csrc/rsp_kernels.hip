@@ -289,11 +289,22 @@ typedef __attribute__((address_space(3))) void lds_void;   // an LDS-DMA destina
 // SGPRs -- the zero padding beyond in_len, the out_len cut and invalid rows (num_records 0)
 // are the hardware range check, with no per-element branch.  G < 64 (N <= 512): rows share
 // a wave, so the accesses stay per-lane predicated.
-template <typename TIn, int N, int G, int SA = 0, bool WS = false, int EARLY = -1>
+//
+// ZIN / ZOUT (wave-uniform rows only, chosen by the host from the segment's lengths): the
+// trailing ZIN of the thread's 16 input slices lie wholly past in_len for every thread of every
+// row and sub-block -- known zero -- and the trailing ZOUT output slices lie wholly past out_len,
+// never stored.  Their echo, gain and store instructions are not issued, and the first forward
+// pass / last inverse pass drop the butterfly operations that only touch them (rsp_fft.h).
+// Every stored value keeps its bit pattern, except that an exact zero may change sign (a dropped
+// `a + 0` passes -0 through where the full form gives +0); |.|^2 and the CFAR cannot see that.
+template <typename TIn, int N, int G, int SA = 0, bool WS = false, int EARLY = -1, int ZIN = 0, int ZOUT = 0>
 __device__ __forceinline__ void pc_row(const TIn* __restrict__ echo, float2* __restrict__ out,
                                        const PcMfArgs& a, int row, int t, float2* buf, int sub = 0) {
     constexpr int E = N / G;
     constexpr bool kUniform = G % 64 == 0;
+    static_assert((ZIN == 0 && ZOUT == 0) || kUniform, "pruned slices need a wave-uniform row");
+    static_assert(ZIN >= 0 && ZIN < E && ZOUT >= 0 && ZOUT < E, "a row keeps at least one slice");
+    constexpr int EI = E - ZIN, EO = E - ZOUT;   // slices that can hold input / are stored
     // Every global load of the row -- MF input and the whole spectrum slice -- is issued up
     // front, so one memory round trip overlaps the FIR (short rows) and the spectrum arrives
     // during the forward FFT instead of after it (N <= 4096: the 32 extra live VGPRs fit the
@@ -337,7 +348,9 @@ __device__ __forceinline__ void pc_row(const TIn* __restrict__ echo, float2* __r
     if constexpr (kUniform) {
         const auto xr = buf_rsrc(x + in_start, valid ? (uint32_t)in_len * ES : 0u);
 #pragma unroll
-        for (int m = 0; m < E; ++m) u[m] = buf_ld_c((const TIn*)nullptr, xr, (uint32_t)e0 * ES, (uint32_t)(G * m) * ES);
+        for (int m = 0; m < EI; ++m) u[m] = buf_ld_c((const TIn*)nullptr, xr, (uint32_t)e0 * ES, (uint32_t)(G * m) * ES);
+#pragma unroll
+        for (int m = EI; m < E; ++m) u[m] = make_float2(0.f, 0.f);
     } else {
 #pragma unroll
         for (int m = 0; m < E; ++m) {
@@ -349,7 +362,7 @@ __device__ __forceinline__ void pc_row(const TIn* __restrict__ echo, float2* __r
         if (a.gain) {   // fused iSTC (rsp_set_prefilter): echo column n times gain[n]
             const auto gr = buf_rsrc(a.gain + in_start, (uint32_t)in_len * 4u);
 #pragma unroll
-            for (int m = 0; m < E; ++m) u[m] = cscale(u[m], buf_ld_f(gr, (uint32_t)e0 * 4u, (uint32_t)(G * m) * 4u));
+            for (int m = 0; m < EI; ++m) u[m] = cscale(u[m], buf_ld_f(gr, (uint32_t)e0 * 4u, (uint32_t)(G * m) * 4u));
         }
     };
     apply_gain();
@@ -373,7 +386,7 @@ __device__ __forceinline__ void pc_row(const TIn* __restrict__ echo, float2* __r
                                 kUniform ? fpre : nullptr);
     }
     RSP_STAMP(0, 2, false);
-    if constexpr (!kDiagPcNoFft) fft_reg_w<N, G, 1, E, 0, NW, WS>(u, buf, t, w);
+    if constexpr (!kDiagPcNoFft) fft_reg_w<N, G, 1, E, 0, NW, WS, ZIN, 0>(u, buf, t, w);
     RSP_STAMP(0, 3, false);
     if constexpr (kEarly) {
 #pragma unroll
@@ -392,12 +405,12 @@ __device__ __forceinline__ void pc_row(const TIn* __restrict__ echo, float2* __r
         }
     }
     RSP_STAMP(0, 4, false);
-    if constexpr (!kDiagPcNoFft) fft_reg_w<N, G, 1, E, 0, NW, WS>(u, buf, t, w);
+    if constexpr (!kDiagPcNoFft) fft_reg_w<N, G, 1, E, 0, NW, WS, 0, ZOUT>(u, buf, t, w);
     RSP_STAMP(0, 5, false);
     if constexpr (kUniform) {
         const auto yr = buf_rsrc(y + out_start, st_ok ? (uint32_t)out_len * 8u : 0u);
 #pragma unroll
-        for (int m = 0; m < E; ++m) buf_st_f2a<SA>(cconj(u[m]), yr, (uint32_t)e0 * 8u, (uint32_t)(G * m) * 8u);
+        for (int m = 0; m < EO; ++m) buf_st_f2a<SA>(cconj(u[m]), yr, (uint32_t)e0 * 8u, (uint32_t)(G * m) * 8u);
     } else if (st_ok) {
 #pragma unroll
         for (int m = 0; m < E; ++m) {
@@ -425,7 +438,10 @@ struct PairCfg {
 // Single segment (N2 == 0) or two independent segments in one launch: blocks
 // [0, nblk2) run segment 2 (the long one, first for a short tail), the rest segment 1.
 // `bid` is the block's index among the PC blocks of the launch.
-template <typename TIn, int N1, int N2>
+// PR packs the pruned slice counts of the two segments, one hex digit each: 0x<ZIN1><ZOUT1><ZIN2><ZOUT2>
+// (pc_row); 0 is the generic instance.
+constexpr int pc_prune_code(int zi1, int zo1, int zi2, int zo2) { return zi1 << 12 | zo1 << 8 | zi2 << 4 | zo2; }
+template <typename TIn, int N1, int N2, int PR = 0>
 __device__ __forceinline__ void pc_mf_block(const TIn* __restrict__ echo, float2* __restrict__ out, const PcMfArgs& a1,
                                             const PcMfArgs& a2, int nblk2, int bid, float2* lds) {
     constexpr int M2 = N2 ? N2 : N1;
@@ -439,7 +455,8 @@ __device__ __forceinline__ void pc_mf_block(const TIn* __restrict__ echo, float2
             const int grp = threadIdx.x / G, t = threadIdx.x % G;
             const int ns = a2.nsub > 1 ? a2.nsub : 1;
             const int u = bid * PC::RPB2 + grp;
-            pc_row<TIn, N2, G, 0, G == 64>(echo, out, a2, u / ns, t, lds + grp * PcCfg<N2>::SLOT, u % ns);
+            pc_row<TIn, N2, G, 0, G == 64, -1, (PR >> 4 & 15), (PR & 15)>(echo, out, a2, u / ns, t,
+                                                                          lds + grp * PcCfg<N2>::SLOT, u % ns);
             return;
         }
     }
@@ -449,16 +466,17 @@ __device__ __forceinline__ void pc_mf_block(const TIn* __restrict__ echo, float2
     const int u = b * PC::RPB1 + grp, ns = a1.nsub > 1 ? a1.nsub : 1;   // (no FIR when ns > 1)
     // a row of one wave (G == 64) synchronises its exchanges within the wave: the rows of a
     // workgroup run independently instead of in barrier lockstep
-    pc_row<TIn, N1, G, 0, G == 64>(echo, out, a1, u / ns, t, lds + grp * PcCfg<N1>::SLOT, u % ns);
+    pc_row<TIn, N1, G, 0, G == 64, -1, (PR >> 12 & 15), (PR >> 8 & 15)>(echo, out, a1, u / ns, t,
+                                                                        lds + grp * PcCfg<N1>::SLOT, u % ns);
 }
 
-template <typename TIn, int N1, int N2>
+template <typename TIn, int N1, int N2, int PR = 0>
 __global__ __launch_bounds__((PairCfg<N1, (N2 ? N2 : N1)>::T), RSP_DIAG_PC_WAVES) void pc_mf_kernel(
     const TIn* __restrict__ echo, float2* __restrict__ out, PcMfArgs a1, PcMfArgs a2, int nblk2) {
     extern __shared__ __attribute__((aligned(16))) float2 lds[];
     RSP_STAMP(0, 0, false);
     RSP_STAMP_RT(0, 8);
-    pc_mf_block<TIn, N1, N2>(echo, out, a1, a2, nblk2, (int)blockIdx.x, lds);
+    pc_mf_block<TIn, N1, N2, PR>(echo, out, a1, a2, nblk2, (int)blockIdx.x, lds);
 }
 
 
@@ -480,21 +498,21 @@ bool pc_mf_supported(int nfft, int fir_stage_len) {
     }
 }
 
-template <typename TIn, int N1, int N2>
+template <typename TIn, int N1, int N2, int PR = 0>
 static hipError_t launch_pc_mf_n(const TIn* echo, float2* out, const PcMfArgs& a1, const PcMfArgs* a2,
                                  hipStream_t s) {
     constexpr int M2 = N2 ? N2 : N1;
     using PC = PairCfg<N1, M2>;
     static LaunchOnce once;
     constexpr size_t lds = PC::lds + kDiagPcLdsExtra;
-    hipError_t e = lds_attr(once, (const void*)pc_mf_kernel<TIn, N1, N2>, lds);
+    hipError_t e = lds_attr(once, (const void*)pc_mf_kernel<TIn, N1, N2, PR>, lds);
     if (e != hipSuccess) return e;
     const int u1 = a1.rows * (a1.nsub > 1 ? a1.nsub : 1);
     const int nblk1 = (u1 + PC::RPB1 - 1) / PC::RPB1;
     const int u2 = a2 ? a2->rows * (a2->nsub > 1 ? a2->nsub : 1) : 0;
     const int nblk2 = N2 ? (u2 + PC::RPB2 - 1) / PC::RPB2 : 0;
     dim3 grid((unsigned)(nblk1 + nblk2)), block(PC::T);
-    hipLaunchKernelGGL((pc_mf_kernel<TIn, N1, N2>), grid, block, lds, s, echo, out, a1, a2 ? *a2 : a1, nblk2);
+    hipLaunchKernelGGL((pc_mf_kernel<TIn, N1, N2, PR>), grid, block, lds, s, echo, out, a1, a2 ? *a2 : a1, nblk2);
     return hipGetLastError();
 }
 
@@ -504,6 +522,15 @@ static hipError_t launch_pc_mf_n(const TIn* echo, float2* out, const PcMfArgs& a
 template <typename TIn>
 static hipError_t launch_pc_mf_t(const TIn* echo, float2* out, const PcMfArgs& a1, const PcMfArgs* a2,
                                  hipStream_t s) {
+    // pruned instances of the built-in presets' 1024/4096 pair (PcMfArgs::zin / zout are what the
+    // lengths allow; an instance that prunes no more than that is valid): v2 at 4096 range bins --
+    // 723 of 1024 and 3145 of 4096 points -- and v2's overlap-save blocks at 8192 / 16384 range
+    // bins, full input and 3397 of 4096 outputs kept.  Anything else runs the generic instance.
+    if (a1.mf.nfft == 1024 && a2 && a2->mf.nfft == 4096 && a1.zin >= 4 && a1.zout >= 4) {
+        if (a2->zin >= 3 && a2->zout >= 3)
+            return launch_pc_mf_n<TIn, 1024, 4096, pc_prune_code(4, 4, 3, 3)>(echo, out, a1, a2, s);
+        if (a2->zout >= 2) return launch_pc_mf_n<TIn, 1024, 4096, pc_prune_code(4, 4, 0, 2)>(echo, out, a1, a2, s);
+    }
     // fused pairs of the built-in presets (v2 at 1024..16384 range bins, legacy)
     RSP_PAIR(1024, 1024);
     RSP_PAIR(1024, 4096);

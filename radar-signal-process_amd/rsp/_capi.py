@@ -31,7 +31,8 @@ EXPORTS = ("rsp_version", "rsp_create", "rsp_destroy", "rsp_last_error", "rsp_se
            "rsp_create_v2", "rsp_create_legacy", "rsp_window_pc_mtd_cfar_dev", "rsp_pc_mtd_cfar_diff_dev",
            "rsp_mtd_cfar_dev", "rsp_set_pc_split", "rsp_set_host_pipeline", "rsp_ingest_record_bytes",
            "rsp_ingest_ddc_dev", "rsp_ingest_frame_dev", "rsp_motion_measure_dev", "rsp_prefilter_dev", "rsp_set_prefilter",
-           "rsp_pc_mtd_cfar_f64", "rsp_cfar_f64", "rsp_set_range_concat", "rsp_score_dev", "rsp_score_summary")
+           "rsp_pc_mtd_cfar_f64", "rsp_cfar_f64", "rsp_set_range_concat", "rsp_score_dev", "rsp_score_summary",
+           "rsp_set_pc_prune", "rsp_set_lane_chunks")
 RSP_NKERNELS = 4
 KERNEL_NAMES = ("pc_kernel", "mtd_kernel", "cfar_r_kernel", "cfar_v_kernel")
 
@@ -157,6 +158,10 @@ def load_library(path=None):
     lib.rsp_set_streams.argtypes = [vp, i32]
     lib.rsp_set_pc_split.restype = C.c_int
     lib.rsp_set_pc_split.argtypes = [vp, i32]
+    lib.rsp_set_pc_prune.restype = C.c_int
+    lib.rsp_set_pc_prune.argtypes = [vp, i32]
+    lib.rsp_set_lane_chunks.restype = C.c_int
+    lib.rsp_set_lane_chunks.argtypes = [vp, C.POINTER(i64), i32]
     lib.rsp_set_host_pipeline.restype = C.c_int
     lib.rsp_set_host_pipeline.argtypes = [vp, i64, i32]
     lib.rsp_set_prefilter.restype = C.c_int

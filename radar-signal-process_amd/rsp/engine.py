@@ -70,10 +70,22 @@ class Engine:
     def set_chunk(self, cpis):
         capi.check(self.lib.rsp_set_chunk(self.ctx, int(cpis)), self.ctx)
 
+    def set_lane_chunks(self, cpis=()):
+        """Per-pipeline chunk sizes in CPIs, one per pipeline (at most 4; the list also sets the
+        pipeline count of non-window chains); () restores the default -- rsp_set_lane_chunks."""
+        n = len(cpis)
+        arr = (C.c_int64 * max(n, 1))(*[int(c) for c in cpis])
+        capi.check(self.lib.rsp_set_lane_chunks(self.ctx, arr, n), self.ctx)
+
     def set_pc_split(self, enable):
         """Overlap-save blocks for matched filters longer than 4096 points (1, the default) or
         whole-length transforms (0) -- rsp_set_pc_split."""
         capi.check(self.lib.rsp_set_pc_split(self.ctx, int(enable)), self.ctx)
+
+    def set_pc_prune(self, enable):
+        """Pulse-compression kernel instances that skip the known-zero input slices and the
+        unstored output slices (1, the default) or the generic instances (0) -- rsp_set_pc_prune."""
+        capi.check(self.lib.rsp_set_pc_prune(self.ctx, int(enable)), self.ctx)
 
     def set_host_pipeline(self, cpis_per_chunk=0, copy_threads=0):
         """Host-buffer calls (pc_mtd_cfar / pc_mtd): CPIs per pipelined chunk and host copy
