@@ -106,7 +106,8 @@ typedef struct {
     int64_t in_len;
     int64_t out_start;     /* output columns [out_start, out_start + out_len) */
     int64_t out_len;       /* FIR: out_len == in_len; MF: out_len <= nfft */
-    int64_t nfft;          /* MF: FFT length, 2^k or 3*2^k, 64 <= nfft <= 16384 */
+    int64_t nfft;          /* MF: FFT length, a power of two, 64 <= nfft <= 16384 (anything
+                              else: RSP_ERR_UNSUPPORTED) */
     double scale;          /* FIR: output scale (1/1.2 for the v2/legacy short pulse);
                               MF: replica scale */
     int64_t coef_len;      /* FIR: taps (<= RSP_MAX_FIR_TAPS); MF: replica length */
@@ -312,6 +313,33 @@ int rsp_set_pc_split(rsp_ctx* ctx, int32_t enable);
  * tests).  Shapes without a built instance run the generic one either way.
  * RSP_ERR_UNSUPPORTED on a context without the specialised PC kernels (nothing to select). */
 int rsp_set_pc_prune(rsp_ctx* ctx, int32_t enable);
+
+/* The pulse-compression launches the context will issue, as chosen from the segment lengths and
+ * the two switches above (read-only; an addition within ABI 5) -- for tests and tools that must
+ * know which kernel path a geometry takes.  One entry per matched-filter segment, in segment
+ * order; the FIR segment rides on the first one's rows (fir = 1). */
+typedef struct {
+    int32_t nfft;      /* transform length the kernel runs: the segment's nfft, or the overlap-save
+                          block length when nsub >= 1 */
+    int32_t nsub;      /* overlap-save blocks per row; 0: the whole segment in one transform */
+    int32_t sub_step;  /* outputs per overlap-save block (nfft - replica length + 1); 0 with nsub 0 */
+    int32_t zin;       /* trailing 1/16-transform slices that are zero padding in every block ... */
+    int32_t zout;      /* ... and that lie past the stored outputs in every block; both 0 for rows
+                          shorter than 1024 points and with rsp_set_pc_prune(ctx, 0) */
+    int32_t fir;       /* 1: this segment's launch also runs the FIR segment */
+} rsp_pc_plan_seg;
+typedef struct {
+    int32_t specialised;   /* 1: the per-segment kernels; 0: the generic kernel, one workgroup per
+                              row for all segments (every other field is then 0) */
+    int32_t fused;         /* 1: both matched filters in one launch (a built pair of lengths) */
+    int32_t prune;         /* pruned instance selected, hex digits <zin1><zout1><zin2><zout2> of the
+                              slices it skips (0x4433, 0x4402); 0: the generic instance */
+    int32_t nmf;           /* matched-filter segments = entries of seg[] filled */
+    rsp_pc_plan_seg seg[RSP_MAX_SEG];
+} rsp_pc_plan_t;
+/* n: the seg[] entries `out` has room for (RSP_MAX_SEG for the struct above); RSP_ERR_ARG when
+ * the context has more matched-filter segments than that. */
+int rsp_pc_plan(rsp_ctx* ctx, rsp_pc_plan_t* out, int32_t n);
 
 /* Range concatenation between pulse compression and the MTD, replacing
  *   Echo_0 = fun_lss_range_concate(prtNum, Echo_0)

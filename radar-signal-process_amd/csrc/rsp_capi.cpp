@@ -963,23 +963,63 @@ int rsp_set_range_concat(rsp_ctx* ctx, int32_t nparts, const int64_t* src_start,
     return RSP_OK;
 }
 
+// The specialised path's launches as run_pc_rows issues them and rsp_pc_plan reports them: both
+// matched filters in one launch where the pair is built, else one launch per segment.
+static bool pc_fused(const rsp_ctx* ctx) {
+    return ctx->pc_mf.size() == 2 && rsp::pc_pair_supported(ctx->pc_mf[0].mf.nfft, ctx->pc_mf[1].mf.nfft);
+}
+static rsp::PcMfArgs pc_launch_args(const rsp_ctx* ctx, size_t i, int64_t rows) {
+    rsp::PcMfArgs a = ctx->pc_mf[i];
+    a.rows = (int)rows;
+    if (!ctx->pc_prune) a.zin = a.zout = 0;
+    return a;
+}
+
 static hipError_t run_pc_rows(rsp_ctx* ctx, const void* ein, int dtype, float2* out, int64_t rows, hipStream_t s) {
     if (!ctx->pc_v2)
         return timed(ctx, RSP_K_PC, s, [&] { return rsp::launch_pc(ein, dtype, out, rows, ctx->pc, ctx->pc_lds, s); });
-    if (ctx->pc_mf.size() == 2 && rsp::pc_pair_supported(ctx->pc_mf[0].mf.nfft, ctx->pc_mf[1].mf.nfft)) {
-        rsp::PcMfArgs a1 = ctx->pc_mf[0], a2 = ctx->pc_mf[1];
-        a1.rows = a2.rows = (int)rows;
-        if (!ctx->pc_prune) a1.zin = a1.zout = a2.zin = a2.zout = 0;
+    if (pc_fused(ctx)) {
+        const rsp::PcMfArgs a1 = pc_launch_args(ctx, 0, rows), a2 = pc_launch_args(ctx, 1, rows);
         return timed(ctx, RSP_K_PC, s, [&] { return rsp::launch_pc_mf(ein, dtype, out, a1, &a2, s); });
     }
-    for (const rsp::PcMfArgs& a0 : ctx->pc_mf) {
-        rsp::PcMfArgs a = a0;
-        a.rows = (int)rows;
-        if (!ctx->pc_prune) a.zin = a.zout = 0;
+    for (size_t i = 0; i < ctx->pc_mf.size(); ++i) {
+        const rsp::PcMfArgs a = pc_launch_args(ctx, i, rows);
         hipError_t e = timed(ctx, RSP_K_PC, s, [&] { return rsp::launch_pc_mf(ein, dtype, out, a, nullptr, s); });
         if (e != hipSuccess) return e;
     }
     return hipSuccess;
+}
+
+int rsp_pc_plan(rsp_ctx* ctx, rsp_pc_plan_t* out, int32_t n) {
+    if (!ctx || !out) return fail(ctx, RSP_ERR_ARG, "rsp_pc_plan: null argument");
+    if (ctx->cfar_only) return fail(ctx, RSP_ERR_ARG, "rsp_pc_plan: CFAR-only context");
+    if (n < 0 || n > RSP_MAX_SEG || (size_t)n < ctx->pc_mf.size())
+        return fail(ctx, RSP_ERR_ARG, "rsp_pc_plan: room for %d segments, the context has %d", n, (int)ctx->pc_mf.size());
+    std::memset(out, 0, sizeof(*out));
+    out->specialised = ctx->pc_v2 ? 1 : 0;
+    if (!ctx->pc_v2) return RSP_OK;
+    out->nmf = (int32_t)ctx->pc_mf.size();
+    out->fused = pc_fused(ctx) ? 1 : 0;
+    for (size_t i = 0; i < ctx->pc_mf.size(); ++i) {
+        const rsp::PcMfArgs a = pc_launch_args(ctx, i, 1);
+        rsp_pc_plan_seg& g = out->seg[i];
+        g.nfft = a.mf.nfft;
+        g.nsub = a.nsub;
+        g.sub_step = a.sub_step;
+        g.zin = a.zin;
+        g.zout = a.zout;
+        g.fir = a.do_fir;
+    }
+    if (out->fused) {
+        const rsp::PcMfArgs a1 = pc_launch_args(ctx, 0, 1), a2 = pc_launch_args(ctx, 1, 1);
+        out->prune = rsp::pc_prune_select(a1, &a2);
+    } else {   // one launch per segment
+        for (size_t i = 0; i < ctx->pc_mf.size(); ++i) {
+            const rsp::PcMfArgs a = pc_launch_args(ctx, i, 1);
+            if (const int pr = rsp::pc_prune_select(a, nullptr)) out->prune = pr;
+        }
+    }
+    return RSP_OK;
 }
 
 int rsp_profile(rsp_ctx* ctx, int32_t enable) {

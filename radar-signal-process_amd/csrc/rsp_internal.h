@@ -224,6 +224,9 @@ hipError_t launch_pc(const void* echo, int dtype, float2* out, int64_t rows, con
 inline int fir_stage_len(const SegDev& g) { return g.ntaps4 - 1 + g.out_len + 4; }
 bool pc_mf_supported(int nfft, int fir_stage_len);
 bool pc_pair_supported(int nfft1, int nfft2);
+// The pruned kernel instance launch_pc_mf runs for (a1, a2), as 0x<ZIN1><ZOUT1><ZIN2><ZOUT2>
+// (pc_row); 0: the generic instance
+int pc_prune_select(const PcMfArgs& a1, const PcMfArgs* a2);
 // a2 == nullptr: one segment; otherwise both segments (a1.mf.nfft, a2->mf.nfft) in one launch
 hipError_t launch_pc_mf(const void* echo, int dtype, float2* out, const PcMfArgs& a1, const PcMfArgs* a2,
                         hipStream_t s);

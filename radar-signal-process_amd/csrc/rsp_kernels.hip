@@ -378,12 +378,18 @@ __device__ __forceinline__ void pc_row(const TIn* __restrict__ echo, float2* __r
         if (a.do_fir) fir_stage_issue<TIn, G>(fpre, x, a.fir, valid, t, t);
     }
     RSP_STAMP(0, 1, true);
+    // columns no segment covers stay 0: the first matched filter's args carry the ranges (nzero is
+    // 0 in every other segment's), with or without a FIR
+    auto zero_fill = [&] {
+        for (int z = 0; z < a.nzero; ++z)
+            for (int c = a.zero_lo[z] + t; c < a.zero_hi[z]; c += G) st_c<SA>(y + c, make_float2(0.f, 0.f));
+    };
     if (a.do_fir) {
-        if (valid)
-            for (int z = 0; z < a.nzero; ++z)
-                for (int c = a.zero_lo[z] + t; c < a.zero_hi[z]; c += G) st_c<SA>(y + c, make_float2(0.f, 0.f));
+        if (valid) zero_fill();
         fir_row<TIn, G, SA, WS>(x, y, a.fir, reinterpret_cast<float*>(buf), valid, t, a.gain, st_ok,
                                 kUniform ? fpre : nullptr);
+    } else if (a.nzero > 0 && valid && sub == 0) {   // no FIR: of an overlap-save split row, sub-block 0
+        zero_fill();
     }
     RSP_STAMP(0, 2, false);
     if constexpr (!kDiagPcNoFft) fft_reg_w<N, G, 1, E, 0, NW, WS, ZIN, 0>(u, buf, t, w);
@@ -519,17 +525,28 @@ static hipError_t launch_pc_mf_n(const TIn* echo, float2* out, const PcMfArgs& a
 #define RSP_PAIR(n1, n2) \
     if (a1.mf.nfft == n1 && a2 && a2->mf.nfft == n2) return launch_pc_mf_n<TIn, n1, n2>(echo, out, a1, a2, s)
 
+// The pruned instance a launch of (a1, a2) runs (0: the generic one) -- the launcher's choice, and
+// what rsp_pc_plan reports.  Instances exist for the built-in presets' 1024/4096 pair
+// (PcMfArgs::zin / zout are what the lengths allow; an instance that prunes no more than that is
+// valid): v2 at 4096 range bins -- 723 of 1024 and 3145 of 4096 points -- and v2's overlap-save
+// blocks at 8192 / 16384 range bins, full input and 3397 of 4096 outputs kept.
+int pc_prune_select(const PcMfArgs& a1, const PcMfArgs* a2) {
+    if (a1.mf.nfft == 1024 && a2 && a2->mf.nfft == 4096 && a1.zin >= 4 && a1.zout >= 4) {
+        if (a2->zin >= 3 && a2->zout >= 3) return pc_prune_code(4, 4, 3, 3);
+        if (a2->zout >= 2) return pc_prune_code(4, 4, 0, 2);
+    }
+    return 0;
+}
+
 template <typename TIn>
 static hipError_t launch_pc_mf_t(const TIn* echo, float2* out, const PcMfArgs& a1, const PcMfArgs* a2,
                                  hipStream_t s) {
-    // pruned instances of the built-in presets' 1024/4096 pair (PcMfArgs::zin / zout are what the
-    // lengths allow; an instance that prunes no more than that is valid): v2 at 4096 range bins --
-    // 723 of 1024 and 3145 of 4096 points -- and v2's overlap-save blocks at 8192 / 16384 range
-    // bins, full input and 3397 of 4096 outputs kept.  Anything else runs the generic instance.
-    if (a1.mf.nfft == 1024 && a2 && a2->mf.nfft == 4096 && a1.zin >= 4 && a1.zout >= 4) {
-        if (a2->zin >= 3 && a2->zout >= 3)
+    switch (pc_prune_select(a1, a2)) {
+        case pc_prune_code(4, 4, 3, 3):
             return launch_pc_mf_n<TIn, 1024, 4096, pc_prune_code(4, 4, 3, 3)>(echo, out, a1, a2, s);
-        if (a2->zout >= 2) return launch_pc_mf_n<TIn, 1024, 4096, pc_prune_code(4, 4, 0, 2)>(echo, out, a1, a2, s);
+        case pc_prune_code(4, 4, 0, 2):
+            return launch_pc_mf_n<TIn, 1024, 4096, pc_prune_code(4, 4, 0, 2)>(echo, out, a1, a2, s);
+        default: break;   // anything else runs the generic instance
     }
     // fused pairs of the built-in presets (v2 at 1024..16384 range bins, legacy)
     RSP_PAIR(1024, 1024);

@@ -32,7 +32,7 @@ EXPORTS = ("rsp_version", "rsp_create", "rsp_destroy", "rsp_last_error", "rsp_se
            "rsp_mtd_cfar_dev", "rsp_set_pc_split", "rsp_set_host_pipeline", "rsp_ingest_record_bytes",
            "rsp_ingest_ddc_dev", "rsp_ingest_frame_dev", "rsp_motion_measure_dev", "rsp_prefilter_dev", "rsp_set_prefilter",
            "rsp_pc_mtd_cfar_f64", "rsp_cfar_f64", "rsp_set_range_concat", "rsp_score_dev", "rsp_score_summary",
-           "rsp_set_pc_prune", "rsp_set_lane_chunks")
+           "rsp_set_pc_prune", "rsp_set_lane_chunks", "rsp_pc_plan")
 RSP_NKERNELS = 4
 KERNEL_NAMES = ("pc_kernel", "mtd_kernel", "cfar_r_kernel", "cfar_v_kernel")
 
@@ -90,6 +90,16 @@ class rsp_score_params(C.Structure):
 class rsp_score_result(C.Structure):
     _fields_ = [("drate", C.c_double), ("acc", C.c_double), ("pof", C.c_double), ("n_valid", C.c_int64),
                 ("n_scored", C.c_int64), ("n_index_error", C.c_int64 * 4), ("n_multi_peak", C.c_int64)]
+
+
+class rsp_pc_plan_seg(C.Structure):
+    _fields_ = [("nfft", C.c_int32), ("nsub", C.c_int32), ("sub_step", C.c_int32), ("zin", C.c_int32),
+                ("zout", C.c_int32), ("fir", C.c_int32)]
+
+
+class rsp_pc_plan_t(C.Structure):
+    _fields_ = [("specialised", C.c_int32), ("fused", C.c_int32), ("prune", C.c_int32), ("nmf", C.c_int32),
+                ("seg", rsp_pc_plan_seg * RSP_MAX_SEG)]
 
 
 # rsp_score_result.n_index_error slots
@@ -160,6 +170,8 @@ def load_library(path=None):
     lib.rsp_set_pc_split.argtypes = [vp, i32]
     lib.rsp_set_pc_prune.restype = C.c_int
     lib.rsp_set_pc_prune.argtypes = [vp, i32]
+    lib.rsp_pc_plan.restype = C.c_int
+    lib.rsp_pc_plan.argtypes = [vp, C.POINTER(rsp_pc_plan_t), i32]
     lib.rsp_set_lane_chunks.restype = C.c_int
     lib.rsp_set_lane_chunks.argtypes = [vp, C.POINTER(i64), i32]
     lib.rsp_set_host_pipeline.restype = C.c_int

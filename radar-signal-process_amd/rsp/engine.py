@@ -87,6 +87,15 @@ class Engine:
         unstored output slices (1, the default) or the generic instances (0) -- rsp_set_pc_prune."""
         capi.check(self.lib.rsp_set_pc_prune(self.ctx, int(enable)), self.ctx)
 
+    def pc_plan(self):
+        """The pulse-compression launches this context issues (rsp_pc_plan): a dict with
+        specialised, fused, prune (the pruned instance's code, 0 = generic) and segs, one
+        (nfft, nsub, sub_step, zin, zout, fir) tuple per matched-filter segment."""
+        p = capi.rsp_pc_plan_t()
+        capi.check(self.lib.rsp_pc_plan(self.ctx, C.byref(p), capi.RSP_MAX_SEG), self.ctx)
+        segs = [(g.nfft, g.nsub, g.sub_step, g.zin, g.zout, g.fir) for g in p.seg[:p.nmf]]
+        return dict(specialised=p.specialised, fused=p.fused, prune=p.prune, segs=segs)
+
     def set_host_pipeline(self, cpis_per_chunk=0, copy_threads=0):
         """Host-buffer calls (pc_mtd_cfar / pc_mtd): CPIs per pipelined chunk and host copy
         threads (0 = the library defaults) -- rsp_set_host_pipeline."""

@@ -14,6 +14,7 @@
  *   - rsp_set_range_concat (fun_lss_range_concate): the RDM of two concatenated column ranges is
  *     the full RDM's columns gathered, bit for bit; a part past the width is RSP_ERR_ARG; 0 parts
  *     restore the full width;
+ *   - rsp_pc_plan: the pulse-compression launches of this shape (the fused, pruned 1024/4096 pair);
  *   - the error contract: a wrong shape is RSP_ERR_SHAPE with a message, a null context
  *     RSP_ERR_ARG.
  * Prints "ok <peak row> <peak column> <detections>" and exits 0, or prints the failed check
@@ -83,6 +84,18 @@ int main(void) {
     uint8_t *fl = malloc(n), *fv = malloc(n), *fl_c = malloc(n), *fv_c = malloc(n);
     int rc = rsp_pc_mtd_cfar(ctx, row, RSP_C128, RSP_ROWMAJOR, P, R, 1, &cf, rdm, RSP_ROWMAJOR, fl, fv);
     CHECK(rc == RSP_OK, "rsp_pc_mtd_cfar row-major: %d %s", rc, rsp_last_error(ctx));
+    {   /* the launches behind it: the 228-sample FIR on the 1024-point rows of segment 2, fused with
+           segment 3's 4096-point rows in the instance pruned for 723 / 3145 samples */
+        rsp_pc_plan_t plan;
+        memset(&plan, 0, sizeof(plan));
+        rc =rsp_pc_plan(ctx, &plan, RSP_MAX_SEG);
+        CHECK(rc == RSP_OK, "rsp_pc_plan: %d %s", rc, rsp_last_error(ctx));
+        CHECK(rc != RSP_OK || (plan.specialised == 1 && plan.fused == 1 && plan.nmf == 2 && plan.prune == 0x4433 &&
+                               plan.seg[0].nfft == 1024 && plan.seg[0].fir == 1 && plan.seg[1].nfft == 4096 &&
+                               plan.seg[1].nsub == 0 && plan.seg[1].zin == 3 && plan.seg[1].zout == 3),
+              "rsp_pc_plan: specialised %d fused %d prune 0x%x, %d segments", plan.specialised, plan.fused,
+              (unsigned)plan.prune, plan.nmf);
+    }
     rc = rsp_pc_mtd_cfar(ctx, col, RSP_C128, RSP_COLMAJOR, P, R, 1, &cf, rdm_c, RSP_COLMAJOR, fl_c, fv_c);
     CHECK(rc == RSP_OK, "rsp_pc_mtd_cfar column-major: %d %s", rc, rsp_last_error(ctx));
     int same = 1;
