@@ -565,6 +565,80 @@ int rsp_prefilter_dev(rsp_ctx* ctx, const void* d_in, void* d_out, int64_t P, in
  * stage: its rows are PC(gain .* x). */
 int rsp_set_prefilter(rsp_ctx* ctx, const float* gain /* nullable, host [R] */, int32_t mti_lag);
 
+/* ---- target injection at a set SCR (fun_SCR / fun_add_clutter) ---------------------------- */
+/* The target-injection step of MatlabProcess_xuzerui/main.m:183-194, which makes the truth R, V
+ * that main_cfar.m's evaluation functions (above) score against, on a device-resident batch of
+ * complex64 [batch][P][R] echoes (row = pulse):
+ *   Echo_simu_STC = fun_SCR(prtNum, Echo_simu, echoData_Frame_0, SCR)      (fun_SCR.m)
+ *       for each segment `points` (1:82, 83:324, 325:1031 with SCRs = SCR + [10 0 0], :23):
+ *           P_s = mean(Echo_simu(1, points).^2) + eps          row 1 only, before any scaling
+ *           for every row i:  P_echo = mean(echo(i, points).^2)
+ *                             g = P_echo * 10^(SCRs/10) / P_s
+ *                             Echo_simu(i, points) = Echo_simu(i, points) * sqrt(g)
+ *       columns in no segment keep their value;
+ *   echo = fun_add_clutter(Echo_simu_STC, echoData_Frame_0)                (fun_add_clutter.m)
+ *       out(i, :) = Echo_simu(i, :) + echo(i, 1:point_prt): the echo may be wider than Echo_simu
+ *       (clutter_ld).
+ * The sums are accumulated in fp64 from the fp32 samples, eps (2^-52) is added in fp64, the gain is
+ * rounded to fp32 once, the scaling product and the clutter add are fp32.  Fixed reduction order,
+ * no atomics: the output is bit-identical from run to run.
+ *
+ * Quirks of the reference:
+ *   - `.^2` of complex I/Q data is the complex square, not |x|^2, so P_s, P_echo and g are complex
+ *     and sqrt(g) is the principal complex root (a result with a zero imaginary part is stored as
+ *     real by MATLAB, so the root of a negative real g is +j sqrt|g|).  The function's header says
+ *     it sets the SCR, so this is an oversight; both behaviours are offered:
+ *       RSP_SCR_ABS2        powers are mean(|x|^2), g is real: the achieved SCR is the set one
+ *                           (the native default);
+ *       RSP_SCR_AS_WRITTEN  complex squares and principal root, exactly as MATLAB evaluates the
+ *                           file (the default of the fun_SCR mirror in rsp/inject.py).
+ *   - the body of fun_SimulateTarget(Velocity, Range, prtNum, pulse1, pulse2, pulse3) is not in
+ *     the reference; only its call survives, commented out, at main.m:188.  It is defined here as
+ *     a point target per segment (the model of rsp/synth.py): the segment's waveform placed at a
+ *     delay column, truncated at the segment's end, and multiplied at pulse m (0-based) by
+ *     exp(j dphi m), dphi = 2 pi (2 v / lambda) PRT.  Its amplitude is irrelevant (the scaling
+ *     normalises it) and its modulus is constant over pulses, so row 1's power is every row's.
+ *
+ * rsp_scr_dev is the general form on arbitrary arrays (16 B read + 8 B written per sample).
+ * rsp_inject_dev is the point-target form: Echo_simu is never materialised (8 B + 8 B per sample);
+ * P_s is computed once per (CPI, segment) from the waveform and the delay.
+ *   d_wf     complex64, the segments' waveforms concatenated: segment s is d_wf[wf_off[s] .. wf_off[s+1])
+ *   d_delay  int32 [batch][RSP_MAX_SEG]: the waveform's first column relative to the segment's
+ *            start; negative (-1) or >= seg_len: no target in that segment
+ *   d_dphi   double [batch]
+ * d_scr_db: double [batch], the SCR of each CPI in dB.
+ * Both are asynchronous on `stream` and work on any context, the CFAR-only kind included.
+ * d_out == d_simu is allowed; d_out == d_clutter only with clutter_batch == batch and clutter_ld == R;
+ * any other overlap of d_out with an input is RSP_ERR_ARG, as are overlapping or out-of-range
+ * segments, nseg outside 0..RSP_MAX_SEG (0: the plain add), clutter_batch outside 1..batch and NULLs.  Uses 16-byte
+ * accesses when R and clutter_ld are even and the buffers 16-byte aligned, 8-byte ones otherwise
+ * (the legacy R = 1031).  R <= 2^24. */
+enum { RSP_SCR_ABS2 = 0, RSP_SCR_AS_WRITTEN = 1 };
+typedef struct {
+    int32_t nseg;                 /* <= RSP_MAX_SEG; 0: no column is scaled (fun_add_clutter alone) */
+    int32_t power;                /* RSP_SCR_* */
+    int32_t add_clutter;          /* 1: out = scaled target + clutter (fun_add_clutter);
+                                     0: the scaled target alone (fun_SCR's return value) */
+    int32_t reserved;             /* 0 */
+    int64_t seg_start[RSP_MAX_SEG], seg_len[RSP_MAX_SEG];   /* disjoint, inside [0, R) */
+    double  seg_db[RSP_MAX_SEG];  /* added to the SCR per segment (reference: 10, 0, 0) */
+    int64_t clutter_ld;           /* clutter row pitch in elements, 0 = R (fun_add_clutter's 1:point_prt) */
+    int64_t clutter_batch;        /* K clutter CPIs, CPI b uses clutter b % K; 0 = batch */
+} rsp_scr_params;
+
+int rsp_scr_dev(rsp_ctx* ctx, const void* d_simu, const void* d_clutter, void* d_out, int64_t P, int64_t R,
+                int64_t batch, const double* d_scr_db /* device [batch] */, const rsp_scr_params* sp,
+                void* stream);
+int rsp_inject_dev(rsp_ctx* ctx, const void* d_clutter, void* d_out, int64_t P, int64_t R, int64_t batch,
+                   const void* d_wf, const int64_t* wf_off /* host [nseg+1] */,
+                   const int32_t* d_delay /* [batch][RSP_MAX_SEG] */, const double* d_dphi,
+                   const double* d_scr_db, const rsp_scr_params* sp, void* stream);
+/* Host only (no GPU, no context): the sums of x^2 (RSP_SCR_AS_WRITTEN: {re, im}) or |x|^2
+ * (RSP_SCR_ABS2: {sum, ignored}) of row 1 of the target and of a clutter row over a segment of n
+ * columns -> the complex gain sqrt(g) = {re, im}.  The same inline function the kernel calls. */
+int rsp_scr_gain(int32_t power, const double sum_simu[2], const double sum_clutter[2], int64_t n,
+                 double scr_db, double gain[2]);
+
 /* ---- diagnostics ---------------------------------------------------------------------- */
 /* Per-kernel device time accumulated from HIP events recorded on the launch stream around
  * kernel launches while profiling is enabled: enable = 1 brackets every launch, enable = N > 1

@@ -84,6 +84,7 @@ struct rsp_ctx {
     DevBuf hit_list;                    // per-lane Doppler-hit lists (fused range CFAR)
     DevBuf hit_ctr;                     // per-lane, per-MTD-workgroup hit counts
     DevBuf meas_band;                   // measurement: per-(CPI, band, column) hit counts
+    DevBuf scr_ps;                      // injection: per-CPI sums, ratios and pulse phases (InjectArgs::ps)
     DevBuf ing_meta;                    // ingest: per-PRT record offsets and types
     DevBuf st_in, st_canon, st_rdm, st_flag, st_flagV, st_t;  // host-API staging (rsp_cfar)
     // Pipelined host-buffer path (rsp_pc_mtd_cfar / rsp_pc_mtd): chunk k's H2D (copy stream),
@@ -330,7 +331,7 @@ int rsp_destroy(rsp_ctx* ctx) {
     for (void* p : ctx->owned) hipFree(p);
     DevBuf* bufs[] = {&ctx->pf_gain, &ctx->scratch_pc, &ctx->cat_tmp, &ctx->tmp_flagV, &ctx->tmp_rdm, &ctx->hit_list, &ctx->hit_ctr,
                       &ctx->st_in, &ctx->st_canon, &ctx->st_rdm, &ctx->st_flag, &ctx->st_flagV, &ctx->st_t,
-                      &ctx->meas_band, &ctx->ing_meta};
+                      &ctx->meas_band, &ctx->ing_meta, &ctx->scr_ps};
     for (DevBuf* b : bufs)
         if (b->p) hipFree(b->p);
     for (auto& e : ctx->evs) {
@@ -1663,6 +1664,132 @@ int rsp_prefilter_dev(rsp_ctx* ctx, const void* d_in, void* d_out, int64_t P, in
     if (!set_device(ctx)) return fail(ctx, RSP_ERR_HIP, "hipSetDevice failed");
     HIP_TRY(ctx, rsp::launch_prefilter((const float2*)d_in, (float2*)d_out, d_gain, (int)P, (int)R, batch, mti_lag,
                                        (hipStream_t)stream));
+    return RSP_OK;
+}
+
+// ------------------------------------------------------------------ target injection at a set SCR
+static bool ranges_overlap(const void* a, int64_t an, const void* b, int64_t bn) {
+    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+    return a0 < b0 + (uintptr_t)bn && b0 < a0 + (uintptr_t)an;
+}
+
+// Everything rsp_scr_dev / rsp_inject_dev can check on the host, before the context is looked at
+// (so a malformed call is told apart without a GPU); fills the shared part of the kernel's arguments.
+static int scr_check(rsp_ctx* ctx, const char* fn, const void* d_simu, bool point, const void* d_clutter, void* d_out,
+                     int64_t P, int64_t R, int64_t batch, const double* d_scr_db, const rsp_scr_params* sp,
+                     rsp::InjectArgs* a, bool* vec16) {
+    if (!sp || !d_clutter || !d_out || !d_scr_db || (!point && !d_simu))
+        return fail(ctx, RSP_ERR_ARG, "%s: null argument", fn);
+    if (P < 1 || R < 1 || batch < 0 || P > (1 << 24) || R > (1 << 24) || batch > 0x7fffffff ||
+        batch * P > ((int64_t)1 << 40))
+        return fail(ctx, RSP_ERR_ARG, "%s: bad shape %lld x %lld x %lld", fn, (long long)batch, (long long)P,
+                    (long long)R);
+    if (sp->nseg < 0 || sp->nseg > RSP_MAX_SEG)
+        return fail(ctx, RSP_ERR_ARG, "%s: nseg %d outside 0..%d", fn, sp->nseg, RSP_MAX_SEG);
+    if ((sp->power != RSP_SCR_ABS2 && sp->power != RSP_SCR_AS_WRITTEN) || (sp->add_clutter != 0 && sp->add_clutter != 1) ||
+        sp->reserved != 0)
+        return fail(ctx, RSP_ERR_ARG, "%s: power %d / add_clutter %d / reserved %d", fn, sp->power, sp->add_clutter,
+                    sp->reserved);
+    for (int s = 0; s < sp->nseg; ++s) {
+        if (sp->seg_start[s] < 0 || sp->seg_len[s] < 1 || sp->seg_start[s] > R || sp->seg_len[s] > R - sp->seg_start[s])
+            return fail(ctx, RSP_ERR_ARG, "%s: segment %d = [%lld, +%lld) is not inside [0, %lld)", fn, s,
+                        (long long)sp->seg_start[s], (long long)sp->seg_len[s], (long long)R);
+        if (!std::isfinite(sp->seg_db[s])) return fail(ctx, RSP_ERR_ARG, "%s: seg_db[%d] is not finite", fn, s);
+        for (int q = 0; q < s; ++q)
+            if (sp->seg_start[s] < sp->seg_start[q] + sp->seg_len[q] && sp->seg_start[q] < sp->seg_start[s] + sp->seg_len[s])
+                return fail(ctx, RSP_ERR_ARG, "%s: segments %d and %d overlap", fn, q, s);
+    }
+    const int64_t ld = sp->clutter_ld ? sp->clutter_ld : R, K = sp->clutter_batch ? sp->clutter_batch : batch;
+    if (ld < R) return fail(ctx, RSP_ERR_ARG, "%s: clutter_ld %lld below R = %lld", fn, (long long)ld, (long long)R);
+    if (batch > 0 && (K < 1 || K > batch))
+        return fail(ctx, RSP_ERR_ARG, "%s: clutter_batch %lld outside 1..%lld", fn, (long long)K, (long long)batch);
+    const int64_t out_bytes = batch * P * R * 8, clut_bytes = ((K * P - 1) * ld + R) * 8;
+    if (batch > 0) {
+        if (d_out == d_clutter) {
+            if (K != batch || ld != R)
+                return fail(ctx, RSP_ERR_ARG, "%s: d_out == d_clutter needs clutter_batch == batch and clutter_ld == R", fn);
+        } else if (ranges_overlap(d_out, out_bytes, d_clutter, clut_bytes)) {
+            return fail(ctx, RSP_ERR_ARG, "%s: d_out overlaps d_clutter", fn);
+        }
+        if (!point && d_out != d_simu && ranges_overlap(d_out, out_bytes, d_simu, out_bytes))
+            return fail(ctx, RSP_ERR_ARG, "%s: d_out overlaps d_simu", fn);
+    }
+    if (((uintptr_t)d_out | (uintptr_t)d_clutter | (uintptr_t)d_simu) & 7)
+        return fail(ctx, RSP_ERR_ARG, "%s: buffers must be 8-byte aligned", fn);
+    *a = rsp::InjectArgs{};
+    a->P = (int)P;
+    a->R = (int)R;
+    a->nseg = sp->nseg;
+    a->power = sp->power;
+    a->add = sp->add_clutter;
+    for (int s = 0; s < sp->nseg; ++s) {
+        a->lo[s] = (int)sp->seg_start[s];
+        a->hi[s] = (int)(sp->seg_start[s] + sp->seg_len[s]);
+        a->db[s] = sp->seg_db[s];
+    }
+    a->c_ld = ld;
+    a->c_cs = P * ld;
+    a->c_batch = (int)(K > 0 ? K : 1);
+    a->simu = (const float2*)d_simu;
+    a->clutter = (const float2*)d_clutter;
+    a->out = (float2*)d_out;
+    a->scr_db = d_scr_db;
+    *vec16 = R % 2 == 0 && ld % 2 == 0 && !(((uintptr_t)d_out | (uintptr_t)d_clutter | (uintptr_t)d_simu) & 15);
+    return RSP_OK;
+}
+
+static int scr_run(rsp_ctx* ctx, rsp::InjectArgs& a, int64_t batch, bool vec16, hipStream_t s) {
+    if (batch == 0) return RSP_OK;
+    if (!set_device(ctx)) return fail(ctx, RSP_ERR_HIP, "hipSetDevice failed");
+    int rc = scratch_acquire(ctx, s);
+    if (rc) return rc;
+    rc = ensure(ctx, ctx->scr_ps, (size_t)batch * (size_t)rsp::inject_ps_stride(a.P) * sizeof(double));
+    if (rc) return rc;
+    a.ps = (double*)ctx->scr_ps.p;
+    HIP_TRY(ctx, rsp::launch_inject(a, batch, vec16, s));
+    return scratch_release(ctx, s);
+}
+
+int rsp_scr_dev(rsp_ctx* ctx, const void* d_simu, const void* d_clutter, void* d_out, int64_t P, int64_t R,
+                int64_t batch, const double* d_scr_db, const rsp_scr_params* sp, void* stream) {
+    rsp::InjectArgs a;
+    bool vec16 = false;
+    const int rc = scr_check(ctx, "rsp_scr_dev", d_simu, false, d_clutter, d_out, P, R, batch, d_scr_db, sp, &a, &vec16);
+    if (rc) return rc;
+    if (!ctx) return fail(nullptr, RSP_ERR_ARG, "rsp_scr_dev: null ctx");
+    return scr_run(ctx, a, batch, vec16, (hipStream_t)stream);
+}
+
+int rsp_inject_dev(rsp_ctx* ctx, const void* d_clutter, void* d_out, int64_t P, int64_t R, int64_t batch,
+                   const void* d_wf, const int64_t* wf_off, const int32_t* d_delay, const double* d_dphi,
+                   const double* d_scr_db, const rsp_scr_params* sp, void* stream) {
+    rsp::InjectArgs a;
+    bool vec16 = false;
+    if (!d_wf || !wf_off || !d_delay || !d_dphi) return fail(ctx, RSP_ERR_ARG, "rsp_inject_dev: null argument");
+    const int rc = scr_check(ctx, "rsp_inject_dev", nullptr, true, d_clutter, d_out, P, R, batch, d_scr_db, sp, &a, &vec16);
+    if (rc) return rc;
+    if (((uintptr_t)d_wf & 7) || ((uintptr_t)d_delay & 3) || ((uintptr_t)d_dphi & 7))
+        return fail(ctx, RSP_ERR_ARG, "rsp_inject_dev: misaligned argument");
+    for (int s = 0; s <= sp->nseg; ++s) {
+        if (wf_off[s] < 0 || wf_off[s] > 0x7fffffff || (s > 0 && wf_off[s] < wf_off[s - 1]))
+            return fail(ctx, RSP_ERR_ARG, "rsp_inject_dev: wf_off[%d] = %lld (offsets must not decrease)", s,
+                        (long long)wf_off[s]);
+        a.wf_off[s] = (int)wf_off[s];
+    }
+    for (int s = sp->nseg + 1; s <= RSP_MAX_SEG; ++s) a.wf_off[s] = a.wf_off[sp->nseg];
+    a.wf = (const float2*)d_wf;
+    a.delay = d_delay;
+    a.dphi = d_dphi;
+    if (!ctx) return fail(nullptr, RSP_ERR_ARG, "rsp_inject_dev: null ctx");
+    return scr_run(ctx, a, batch, vec16, (hipStream_t)stream);
+}
+
+int rsp_scr_gain(int32_t power, const double sum_simu[2], const double sum_clutter[2], int64_t n, double scr_db,
+                 double gain[2]) {
+    if (!sum_simu || !sum_clutter || !gain || n < 1 || (power != RSP_SCR_ABS2 && power != RSP_SCR_AS_WRITTEN))
+        return fail(nullptr, RSP_ERR_ARG, "rsp_scr_gain: bad argument");
+    rsp::scr_gain(power, sum_simu[0], sum_simu[1], sum_clutter[0], sum_clutter[1], (double)n, rsp::scr_lin(scr_db), &gain[0],
+                  &gain[1]);
     return RSP_OK;
 }
 

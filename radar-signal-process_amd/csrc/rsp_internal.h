@@ -2,6 +2,7 @@
 // HIP kernels (rsp_kernels.hip).  Not part of the public ABI.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <math.h>
 #include <stdint.h>
 
 #include <mutex>
@@ -180,6 +181,71 @@ hipError_t launch_score(const uint8_t* flag, const float* rdm, const int32_t* tr
 // Echo pre-filters (rsp_prefilter.hip): iSTC gain per range bin and/or MTI row difference.
 hipError_t launch_prefilter(const float2* in, float2* out, const float* gain, int P, int R, int64_t batch, int lag,
                             hipStream_t st);
+
+// Target injection at a set SCR (rsp_inject.hip): fun_SCR.m / fun_add_clutter.m.
+// 10^(SCR/10), the power ratio of a SCR in dB (fun_SCR.m:23).
+__host__ __device__ inline double scr_lin(double scr_db) { return pow(10.0, scr_db / 10.0); }
+// The gain sqrt(g) of one (row, segment) from the sums of x^2 (RSP_SCR_AS_WRITTEN: complex) or
+// |x|^2 (RSP_SCR_ABS2: real, the imaginary sums are ignored) over the segment's n columns and
+// the ratio k = scr_lin(SCR):
+//   P_s = mean(simu row 1) + eps, P_echo = mean(clutter row), g = P_echo * k / P_s,
+// and the principal root.  MATLAB stores a result whose imaginary part is zero as real, so the
+// root of a negative real g is +j sqrt|g| whatever the sign of that zero.  The row kernel and the
+// host export rsp_scr_gain both call this (and scr_lin).
+__host__ __device__ inline void scr_gain(int power, double ss_re, double ss_im, double sc_re, double sc_im, double n,
+                                         double k, double* g_re, double* g_im) {
+    const double eps = 2.220446049250313e-16;   // MATLAB's eps, 2^-52
+    const double ps_re = ss_re / n + eps, pe_re = sc_re / n * k;
+    double q_re, q_im = 0.0;
+    if (power == RSP_SCR_AS_WRITTEN) {
+        const double ps_im = ss_im / n, pe_im = sc_im / n * k;
+        const double den = ps_re * ps_re + ps_im * ps_im;
+        q_re = (pe_re * ps_re + pe_im * ps_im) / den;
+        q_im = (pe_im * ps_re - pe_re * ps_im) / den;
+    } else {
+        q_re = pe_re / ps_re;
+    }
+    const double r = sqrt(q_re * q_re + q_im * q_im);   // |g| stays far inside the fp64 range
+    if (r == 0.0) {
+        *g_re = 0.0;
+        *g_im = 0.0;
+    } else if (q_re >= 0.0) {
+        const double t = sqrt(0.5 * (r + q_re));
+        *g_re = t;
+        *g_im = q_im / (2.0 * t);
+    } else {
+        const double t = sqrt(0.5 * (r - q_re));
+        *g_re = fabs(q_im) / (2.0 * t);
+        *g_im = q_im < 0.0 ? -t : t;
+    }
+}
+
+struct InjectArgs {
+    int P, R;
+    int nseg, power, add;
+    int lo[RSP_MAX_SEG], hi[RSP_MAX_SEG];   // segment columns [lo, hi)
+    double db[RSP_MAX_SEG];
+    int64_t c_ld, c_cs;                     // clutter row pitch and CPI stride, in elements
+    int c_batch;                            // CPI b reads clutter CPI b % c_batch
+    const float2* simu;                     // general form; null in the point-target form
+    const float2* clutter;
+    float2* out;
+    const double* scr_db;                   // [batch]
+    // context scratch, inject_ps_stride(P) doubles per CPI: [RSP_MAX_SEG][4] = {row 1's sums re, im,
+    // scr_lin(SCR + seg_db), 0}, then (point-target form) [P][2] = cos, sin of dphi * m
+    double* ps;
+    // point-target form
+    const float2* wf;
+    int wf_off[RSP_MAX_SEG + 1];
+    const int32_t* delay;                   // [batch][RSP_MAX_SEG]
+    const double* dphi;                     // [batch]
+};
+// Complex samples of a row the row kernel keeps in registers per thread; longer rows are read a
+// second time (from L2) for the scaling pass.
+constexpr int kInjectRegVec = 8;            // 8- or 16-byte accesses per thread
+constexpr int64_t inject_ps_stride(int64_t P) { return 4 * RSP_MAX_SEG + 2 * P; }
+// vec16: 16-byte accesses (R, c_ld even and the buffers 16-byte aligned)
+hipError_t launch_inject(const InjectArgs& a, int64_t batch, bool vec16, hipStream_t st);
 
 struct IngestArgs {
     int prt_num, point_prt, channel_num, beam_num;

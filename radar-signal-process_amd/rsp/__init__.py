@@ -4,7 +4,8 @@ The compute lives in lib/librsp.so (HIP kernels for gfx950 behind the C ABI of
 include/rsp.h); this package is the Python mirror of the reference's MATLAB interface
 (rsp.matlab), parameter presets (rsp.presets), the Engine wrapper (rsp.engine), the
 deterministic synthetic-echo generator (rsp.synth) and, behind the chain, the per-hit
-measurement (rsp.measure) and the scoring of detections against truth (rsp.score).
+measurement (rsp.measure), the scoring of detections against truth (rsp.score) and, in
+front of it, the injection of simulated targets at a set SCR (rsp.inject).
 """
 from . import _capi, presets, synth  # noqa: F401
 from ._capi import RspError, load_library  # noqa: F401

@@ -32,7 +32,7 @@ EXPORTS = ("rsp_version", "rsp_create", "rsp_destroy", "rsp_last_error", "rsp_se
            "rsp_mtd_cfar_dev", "rsp_set_pc_split", "rsp_set_host_pipeline", "rsp_ingest_record_bytes",
            "rsp_ingest_ddc_dev", "rsp_ingest_frame_dev", "rsp_motion_measure_dev", "rsp_prefilter_dev", "rsp_set_prefilter",
            "rsp_pc_mtd_cfar_f64", "rsp_cfar_f64", "rsp_set_range_concat", "rsp_score_dev", "rsp_score_summary",
-           "rsp_set_pc_prune", "rsp_set_lane_chunks", "rsp_pc_plan")
+           "rsp_set_pc_prune", "rsp_set_lane_chunks", "rsp_pc_plan", "rsp_scr_dev", "rsp_inject_dev", "rsp_scr_gain")
 RSP_NKERNELS = 4
 KERNEL_NAMES = ("pc_kernel", "mtd_kernel", "cfar_r_kernel", "cfar_v_kernel")
 
@@ -101,6 +101,15 @@ class rsp_pc_plan_t(C.Structure):
     _fields_ = [("specialised", C.c_int32), ("fused", C.c_int32), ("prune", C.c_int32), ("nmf", C.c_int32),
                 ("seg", rsp_pc_plan_seg * RSP_MAX_SEG)]
 
+
+class rsp_scr_params(C.Structure):
+    _fields_ = [("nseg", C.c_int32), ("power", C.c_int32), ("add_clutter", C.c_int32), ("reserved", C.c_int32),
+                ("seg_start", C.c_int64 * RSP_MAX_SEG), ("seg_len", C.c_int64 * RSP_MAX_SEG),
+                ("seg_db", C.c_double * RSP_MAX_SEG), ("clutter_ld", C.c_int64), ("clutter_batch", C.c_int64)]
+
+
+# rsp_scr_params.power
+RSP_SCR_ABS2, RSP_SCR_AS_WRITTEN = 0, 1
 
 # rsp_score_result.n_index_error slots
 RSP_SCORE_FA, RSP_SCORE_DRATE, RSP_SCORE_ACC, RSP_SCORE_PCF = range(4)
@@ -192,6 +201,14 @@ def load_library(path=None):
     lib.rsp_score_summary.restype = C.c_int
     lib.rsp_score_summary.argtypes = [vp, vp, i64, i64, i64, C.POINTER(rsp_score_params), vp,
                                       C.POINTER(rsp_score_result)]
+    lib.rsp_scr_dev.restype = C.c_int
+    lib.rsp_scr_dev.argtypes = [vp, vp, vp, vp, i64, i64, i64, vp, C.POINTER(rsp_scr_params), vp]
+    lib.rsp_inject_dev.restype = C.c_int
+    lib.rsp_inject_dev.argtypes = [vp, vp, vp, i64, i64, i64, vp, C.POINTER(i64), vp, vp, vp,
+                                   C.POINTER(rsp_scr_params), vp]
+    lib.rsp_scr_gain.restype = C.c_int
+    lib.rsp_scr_gain.argtypes = [i32, C.POINTER(C.c_double), C.POINTER(C.c_double), i64, C.c_double,
+                                 C.POINTER(C.c_double)]
     lib.rsp_prefilter_dev.restype = C.c_int
     lib.rsp_prefilter_dev.argtypes = [vp, vp, vp, i64, i64, i64, vp, i32, vp]
     lib.rsp_profile.restype = C.c_int

@@ -18,6 +18,9 @@ threshold loop (:40), with the reference's names and argument meaning:
     :183-184 (first bin of a tie) and the validity gate, 0-based.
   * sweep(engine, echo_dev, truth_idx, T_values, cfar): main_cfar.m:40-58's threshold loop on a
     device-resident batch; only the batch x 8 records cross PCIe.
+  * scr_sweep(engine, clutter_dev, plan, SCR_values, cfar, seg): the Pd-versus-SCR loop: for
+    each SCR the plan's targets are injected into the clutter on the device (rsp.inject), the
+    chain and the CFAR run, and the flags are scored against the plan's truth cells.
 
 Quirks of the reference kept as they are: `for i=1:length(cfarFlag_all)` is the largest
 dimension of the 3-D array (here the loop runs over the batch, the first dimension), and
@@ -254,4 +257,38 @@ def sweep(engine, echo_dev, truth_idx, T_values, cfar, params=None, on_step=None
         if on_step is not None:
             on_step(T, flag, rdm, rec)
         out.append(dict(T=T, **summary(rec, truth_idx, V, R, params, lib=engine.lib)))
+    return out
+
+
+def scr_sweep(engine, clutter_dev, plan, SCR_values, cfar, seg=0, params=None, on_step=None, power=None):  # noqa: N803
+    """Detection scores over a sweep of signal-to-clutter ratios, everything in device memory:
+    for each SCR [dB] the plan's point targets (rsp.inject.target_plan, one per CPI) are injected
+    into clutter_dev ([K][P][R] complex64, K <= plan.batch) at that SCR into one reused buffer
+    (rsp_inject_dev), the chain runs with `cfar` (Engine.run_dev) and the flags are scored against
+    plan.truth_cells(spec, seg), the target in pulse-compression segment `seg`.  Only the batch x 8
+    records cross PCIe.  params: default the reference's box sizes with v_lim, r_lim = the RDM's
+    own size.  on_step(SCR, flag, rdm, rec), if given, sees each step's device tensors.  Returns
+    [dict(SCR=SCR, **summary)] in the order of SCR_values."""
+    import torch
+    from . import inject
+    spec = engine.spec
+    B = plan.batch
+    V, R = spec.V, spec.R_out
+    dev = clutter_dev.device
+    truth = plan.truth_cells(spec, seg)
+    echo = torch.empty((B, spec.P, spec.R), dtype=torch.complex64, device=dev)
+    rdm = torch.empty((B, V, R), dtype=torch.float32, device=dev)
+    flag = torch.empty((B, V, R), dtype=torch.uint8, device=dev)
+    if params is None:
+        params = score_params(v_lim=V, r_lim=R)
+    inj = inject.Injector(engine=engine)
+    scorer = Scorer(engine=engine)
+    out = []
+    for scr in SCR_values:
+        inj.inject_dev(clutter_dev, plan, float(scr), out=echo, power=inject.ABS2 if power is None else power)
+        engine.run_dev(echo, rdm=rdm, flag=flag, cfar=cfar)
+        rec = scorer.score_dev(flag, rdm, truth, params)
+        if on_step is not None:
+            on_step(scr, flag, rdm, rec)
+        out.append(dict(SCR=scr, **summary(rec, truth, V, R, params, lib=engine.lib)))
     return out
