@@ -341,6 +341,52 @@ typedef struct {
  * the context has more matched-filter segments than that. */
 int rsp_pc_plan(rsp_ctx* ctx, rsp_pc_plan_t* out, int32_t n);
 
+/* The CFAR kernels a call would run (read-only; an addition within ABI 5), from the same host
+ * predicates the launchers use -- for tests and tools that must know which path a shape, a window
+ * and a chunk plan take.  Nothing is launched and no buffer is touched. */
+enum { RSP_CFAR_R_COPY = 0,      /* rFlag == 0: flag = flagV */
+       RSP_CFAR_R_GENERIC = 1,   /* any window: one workgroup per row, the row staged in LDS */
+       RSP_CFAR_R_4CELL = 2,     /* ref 5 / guard 7, R % 4 == 0: four cells per thread */
+       RSP_CFAR_R_16CELL = 3 };  /* ref 5 / guard 7, R % 16 == 0: sixteen cells per thread */
+enum { RSP_RANGE_NONE = 0,       /* rFlag == 0: the MTD launch writes flag = flagV */
+       RSP_RANGE_GROUPED = 1,    /* one hit-list launch behind up to 16 chunks of a pipeline */
+       RSP_RANGE_JOB57 = 2,      /* inside the pipeline's next MTD launch: a region's first `threads`
+                                    hits with the tile's loads, the rest in a tail after the tile */
+       RSP_RANGE_PREV_HITS = 3,  /* inside the pipeline's next MTD launch, after its tile */
+       RSP_RANGE_PER_CHUNK = 4 };/* a hit-list launch behind every chunk's MTD */
+enum { RSP_HITS_NONE = 0,
+       RSP_HITS_BATCHED57 = 1,       /* ref 5 / guard 7, hit_lanes lanes per region */
+       RSP_HITS_PER_HIT57 = 2,       /* ref 5 / guard 7, a workgroup per region, a thread per hit */
+       RSP_HITS_PER_HIT_RUNTIME = 3 };/* any window, likewise */
+typedef struct {
+    int32_t fused;            /* the call asked about: 0 rsp_cfar / rsp_cfar_dev, 1 the chain */
+    /* fused == 0 (the chain's fields are 0) */
+    int32_t v_tile_log2;      /* log2 of the Doppler kernel's tile width in range bins */
+    int32_t r_kernel;         /* RSP_CFAR_R_* */
+    int32_t r_groups;         /* workgroups per row of the 4- / 16-cell kernels, else 0 */
+    /* fused == 1 (the three fields above are 0) */
+    int32_t window_compiled;  /* 1: the Doppler window is compiled into the MTD kernel (5 + 7) */
+    int32_t bluestein;        /* Bluestein convolution length, 0 for a radix transform */
+    int32_t tile_w;           /* range bins per MTD workgroup */
+    int32_t threads;          /* threads per MTD workgroup */
+    int32_t region;           /* hit-list entries per workgroup = tile_w * P */
+    int32_t nchunks;          /* MTD launches of the call */
+    int32_t nlanes;           /* chunk pipelines used */
+    int32_t lane_chunk[4];    /* CPIs of a full chunk of each pipeline (0: pipeline unused) */
+    int32_t lane_last[4];     /* CPIs of each pipeline's last chunk (the call's final chunk may be short) */
+    int32_t range_stage;      /* RSP_RANGE_*: where a chunk's range stage runs; a pipeline's last chunk
+                                 (and with RSP_RANGE_GROUPED every group) gets a hit-list launch */
+    int32_t hit_kernel;       /* RSP_HITS_* of those launches (sized for the largest one) */
+    int32_t hit_lanes;        /* lanes per region of RSP_HITS_BATCHED57 (16, 32, 64, 256), else 0 */
+    int32_t flag_memset;      /* 1: the flag background is a memset, 0: the MTD kernel's stores */
+} rsp_cfar_plan_t;
+/* V, R, batch and cfar as for the call itself.  fused = 0: rsp_cfar_dev(ctx, ..., V, R, batch, cfar).
+ * fused = 1: rsp_mtd_cfar_dev / rsp_pc_mtd_cfar_dev(ctx, ..., batch, cfar) with (with_rdm != 0) or
+ * without a caller's RDM buffer; V and R must be the context's Doppler rows and R_out.  Returns
+ * what that call's validation would return (RSP_ERR_ARG, RSP_ERR_CFAR_WINDOW, RSP_ERR_UNSUPPORTED). */
+int rsp_cfar_plan(rsp_ctx* ctx, int64_t V, int64_t R, int64_t batch, const rsp_cfar_params* cfar,
+                  int32_t fused, int32_t with_rdm, rsp_cfar_plan_t* out);
+
 /* Range concatenation between pulse compression and the MTD, replacing
  *   Echo_0 = fun_lss_range_concate(prtNum, Echo_0)
  * (MatlabProcess_xuzerui/fun_lss_range_concate.m:4-7, called at main.m:210-211 -- and commented

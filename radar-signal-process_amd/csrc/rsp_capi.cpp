@@ -1148,22 +1148,27 @@ static int range_group() {
     return g;
 }
 
-static int run_chain_body(rsp_ctx* ctx, const void* d_echo, int32_t dtype, int64_t units, int win,
-                          const rsp_cfar_params* cfar, float* d_rdm, uint8_t* d_flag, uint8_t* d_flagV,
-                          float* d_diff, hipStream_t s, bool pc_input) {
-    const int64_t P = ctx->p.P, R = ctx->p.R, Ro = ctx->p.R_out, V = ctx->V, NB = ctx->beams;
-    const size_t esz = dtype == RSP_C64 ? 8 : 4;
-    rsp::MtdArgs m = ctx->mtd;
-    rsp::CfarRArgs cr{};
-    if (cfar) {
-        int rc = build_cfar(ctx, cfar, V, Ro, &m.cv, &cr);
-        if (rc) return rc;
-    } else {
-        m.cv.enabled = 0;
-    }
+// The chunk plan and the range-stage choices of one chain call over `units` (run_chain_body's
+// arguments): run_chain_body launches by it and rsp_cfar_plan reports it.
+struct ChainLayout {
+    int64_t ocpi = 1;                 // output CPIs per unit
+    rsp::ChunkPlan plan;
+    size_t plane = 0;                 // output cells per CPI
+    size_t cells = 0;                 // output cells per chunk slot
+    size_t pcrows = 0;                // PC rows of the call's largest chunk
+    int nreg[rsp::kMaxLanes] = {};    // hit-list regions of a lane's full chunk
+    int reg = 0;                      // entries per region
+    size_t nreg_all = 0;              // all lanes' regions together
+    int rgrp = 1;                     // chunks per range-stage group
+    bool grouped = false;             // the range stages run as one launch per group
+    int spl = 2;                      // hit-list slots per lane
+    bool fm = false;                  // the flag background is a memset before the MTD
+};
+static int chain_layout(rsp_ctx* ctx, int64_t units, int win, bool cfar, const rsp::CfarRArgs& cr, bool have_rdm,
+                        bool have_flag, ChainLayout* L) {
+    const int64_t P = ctx->p.P, Ro = ctx->p.R_out, V = ctx->V, NB = ctx->beams;
     const int64_t ocpi = win > 0 ? win : 1;               // output CPIs per unit
-    m.nwin = win;
-    for (int i = 0; i < win; ++i) m.win_start[i] = (int)mround((double)i * P / win);
+    L->ocpi = ocpi;
     int64_t cu = chunk_of(ctx, units * ocpi);              // CPIs per chunk
     // Default pipelines: 2 (PC of one chunk overlaps MTD / CFAR of the other); window mode 1 with
     // chunks of >= 32 frame pairs (look-ahead PC overhead <= 1/32, fewer launch tails): c4 114.9k
@@ -1200,24 +1205,18 @@ static int run_chain_body(rsp_ctx* ctx, const void* d_echo, int32_t dtype, int64
             lcu[1] = b;
         }
     }
-    const rsp::ChunkPlan plan = rsp::plan_chunks(units, lcu, nlanes);
-    const std::vector<int64_t>& cstart = plan.cstart;
-    const int64_t nchunks = plan.nchunks();
+    L->plan = rsp::plan_chunks(units, lcu, nlanes);
+    const rsp::ChunkPlan& plan = L->plan;
     const int ns = plan.ns;
     const size_t plane = (size_t)V * Ro;                  // output cells per CPI
+    L->plane = plane;
     // concat staging and internal RDM slots are sized by the call's largest chunk; a lane's PC
     // scratch slot by the lane's own (16 / 24 CPIs at c3: 160 MiB of scratch, not 192)
     const size_t cells = (size_t)plan.cap_max * ocpi * plane;       // output cells per chunk slot
-    const size_t pcrows = (size_t)(plan.cap_max + (win > 0 ? 1 : 0)) * NB * P;
-    size_t pcoff[rsp::kMaxLanes + 1] = {};   // first PC scratch row of each lane's slot
-    for (int l = 0; l < ns; ++l) pcoff[l + 1] = pcoff[l] + (size_t)(plan.cap[l] + (win > 0 ? 1 : 0)) * NB * P;
-    int rc = pc_input ? RSP_OK : ensure(ctx, ctx->scratch_pc, pcoff[ns] * Ro * sizeof(float2));
-    if (rc) return rc;
-    if (!pc_input && (rc = cat_ensure(ctx, ns, (int64_t)pcrows))) return rc;
+    L->cells = cells;
+    L->pcrows = (size_t)(plan.cap_max + (win > 0 ? 1 : 0)) * NB * P;
     // hit-list regions of a lane's full chunk (nreg[lane], each `reg` indices: the region is one MTD
     // workgroup's cells, whatever the chunk size), and all lanes' together
-    int nreg[rsp::kMaxLanes] = {}, reg = 0;
-    size_t nreg_all = 0;
     if (cfar) {
         // fused range stage: per-lane hit lists, one region per MTD workgroup sized to its
         // cells (no overflow, no global atomics), and per-workgroup counts
@@ -1225,25 +1224,76 @@ static int run_chain_body(rsp_ctx* ctx, const void* d_echo, int32_t dtype, int64
         // two slots per lane: chunk k's list is read by the next MTD launch on its lane while
         // that launch fills the other slot
         for (int l = 0; l < ns; ++l) {
-            rsp::mtd_regions((int)V, (int)Ro, (int)(plan.cap[l] * ocpi), &nreg[l], &reg, (int)NB);
-            nreg_all += (size_t)nreg[l];
+            rsp::mtd_regions((int)V, (int)Ro, (int)(plan.cap[l] * ocpi), &L->nreg[l], &L->reg, (int)NB);
+            L->nreg_all += (size_t)L->nreg[l];
         }
     }
     // grouped range stages (range_mode 2): a group's outputs must stay inside the range kernels'
     // 2 GiB buffer window, and the RDM must be the caller's (internal RDM slots are reused)
     int rgrp = range_group();
-    if (cfar && nreg_all > 0) {   // the groups' hit-list slots within kRangeGroupBytes
-        const uint64_t round_bytes = (uint64_t)nreg_all * (uint64_t)reg * 4u;   // one slot of every lane
+    if (cfar && L->nreg_all > 0) {   // the groups' hit-list slots within kRangeGroupBytes
+        const uint64_t round_bytes = (uint64_t)L->nreg_all * (uint64_t)L->reg * 4u;   // one slot of every lane
         const uint64_t fit = kRangeGroupBytes / round_bytes;
         if ((uint64_t)rgrp > fit) rgrp = fit > 0 ? (int)fit : 1;
     }
+    L->rgrp = rgrp;
     // a lane's group spans rgrp - 1 whole rounds over the lanes plus its own last chunk
-    const bool grouped = cfar && cr.rflag && d_rdm && range_mode() == 2 && rgrp > 1 &&
-                         ((uint64_t)(rgrp - 1) * (uint64_t)plan.period * ocpi * plane + (uint64_t)cells) * 4u <
-                             0x80000000ull;   // (kOob, rsp_buf.h)
+    L->grouped = cfar && cr.rflag && have_rdm && range_mode() == 2 && rgrp > 1 &&
+                 ((uint64_t)(rgrp - 1) * (uint64_t)plan.period * ocpi * plane + (uint64_t)cells) * 4u <
+                     0x80000000ull;   // (kOob, rsp_buf.h)
     // hit-list slots per lane: grouped, a group's range launch is stream-ordered before the next
     // group's first MTD on the lane, so the next group reuses the slots
-    const int spl = grouped ? rgrp : 2;
+    L->spl = L->grouped ? rgrp : 2;
+    // The flag background: the MTD kernels' own stores, except for big chunks of long tiles: there a
+    // memset of the chunk's flag plane on the lane before its MTD (a streaming fill) beats the tiles'
+    // 16-byte row-segment stores (tiles of P >= 256 are 16 bins wide).  c4 (one 268 MB chunk per step): MTD 649 -> 572 us, +4.3 %;
+    // c3 (32-bin tiles, 8 MiB chunks) -2.8 %, c5 (8 MiB chunks) neutral
+    // (profiles/r05/ab/flag_memset.txt).  Dev A/B: RSP_FLAG_MEMSET 0 / 1 forces it off / on.
+    static const int fenv = [] { const char* v = getenv("RSP_FLAG_MEMSET"); return v && *v ? atoi(v) : -1; }();
+    L->fm = cfar && cr.rflag && have_flag &&
+            (fenv >= 0 ? fenv == 1 : (V >= 256 && (uint64_t)cells >= (64ull << 20)));
+    // (The fill on a side stream beside the chunk's PC, joined before the MTD, measured the same:
+    // c4 133.8k vs 134.2k windows/s, three interleaved pairs, bit-identical -- the fill and the
+    // PC share the HBM; profiles/r06/c4/flag_memset_side.txt.)
+    return RSP_OK;
+}
+
+// RSP_RANGE_MODE=1: a hit-list launch behind every chunk's MTD (where grouping does not apply)
+static bool range_per_chunk(const ChainLayout& L) { return !L.grouped && range_mode() == 1; }
+
+static int run_chain_body(rsp_ctx* ctx, const void* d_echo, int32_t dtype, int64_t units, int win,
+                          const rsp_cfar_params* cfar, float* d_rdm, uint8_t* d_flag, uint8_t* d_flagV,
+                          float* d_diff, hipStream_t s, bool pc_input) {
+    const int64_t P = ctx->p.P, R = ctx->p.R, Ro = ctx->p.R_out, V = ctx->V, NB = ctx->beams;
+    const size_t esz = dtype == RSP_C64 ? 8 : 4;
+    rsp::MtdArgs m = ctx->mtd;
+    rsp::CfarRArgs cr{};
+    if (cfar) {
+        int rc = build_cfar(ctx, cfar, V, Ro, &m.cv, &cr);
+        if (rc) return rc;
+    } else {
+        m.cv.enabled = 0;
+    }
+    m.nwin = win;
+    for (int i = 0; i < win; ++i) m.win_start[i] = (int)mround((double)i * P / win);
+    ChainLayout L;
+    int rc = chain_layout(ctx, units, win, cfar != nullptr, cr, d_rdm != nullptr, d_flag != nullptr, &L);
+    if (rc) return rc;
+    const int64_t ocpi = L.ocpi;                           // output CPIs per unit
+    const rsp::ChunkPlan& plan = L.plan;
+    const std::vector<int64_t>& cstart = plan.cstart;
+    const int64_t nchunks = plan.nchunks();
+    const int ns = plan.ns;
+    const size_t plane = L.plane, cells = L.cells, pcrows = L.pcrows;
+    const int* nreg = L.nreg;
+    const int reg = L.reg, rgrp = L.rgrp, spl = L.spl;
+    const size_t nreg_all = L.nreg_all;
+    const bool grouped = L.grouped, fm = L.fm;
+    size_t pcoff[rsp::kMaxLanes + 1] = {};   // first PC scratch row of each lane's slot
+    for (int l = 0; l < ns; ++l) pcoff[l + 1] = pcoff[l] + (size_t)(plan.cap[l] + (win > 0 ? 1 : 0)) * NB * P;
+    rc = pc_input ? RSP_OK : ensure(ctx, ctx->scratch_pc, pcoff[ns] * Ro * sizeof(float2));
+    if (rc) return rc;
+    if (!pc_input && (rc = cat_ensure(ctx, ns, (int64_t)pcrows))) return rc;
     // lane l's slots start behind those of the lanes before it, each lane's sized by its own regions
     size_t hbase[rsp::kMaxLanes] = {};
     for (int l = 1; l < ns; ++l) hbase[l] = hbase[l - 1] + (size_t)spl * nreg[l - 1];
@@ -1259,20 +1309,9 @@ static int run_chain_body(rsp_ctx* ctx, const void* d_echo, int32_t dtype, int64
     }
     // the MTD kernels write the flag plane's zero background with the Doppler stage (every cell
     // of a CPI belongs to one MTD thread), and the range stage, stream-ordered after that
-    // chunk's MTD launch, writes the 1s: no separate fill pass
-    m.flag_zero = 1;
-    // ... except for big chunks of long tiles: there a memset of the chunk's flag plane on the
-    // lane before its MTD (a streaming fill) beats the tiles' 16-byte row-segment stores (tiles of
-    // P >= 256 are 16 bins wide).  c4 (one 268 MB chunk per step): MTD 649 -> 572 us, +4.3 %;
-    // c3 (32-bin tiles, 8 MiB chunks) -2.8 %, c5 (8 MiB chunks) neutral
-    // (profiles/r05/ab/flag_memset.txt).  Dev A/B: RSP_FLAG_MEMSET 0 / 1 forces it off / on.
-    static const int fenv = [] { const char* v = getenv("RSP_FLAG_MEMSET"); return v && *v ? atoi(v) : -1; }();
-    const bool fm = cfar && cr.rflag && d_flag &&
-                    (fenv >= 0 ? fenv == 1 : (V >= 256 && (uint64_t)cells >= (64ull << 20)));
-    if (fm) m.flag_zero = 0;
-    // (The fill on a side stream beside the chunk's PC, joined before the MTD, measured the same:
-    // c4 133.8k vs 134.2k windows/s, three interleaved pairs, bit-identical -- the fill and the
-    // PC share the HBM; profiles/r06/c4/flag_memset_side.txt.)
+    // chunk's MTD launch, writes the 1s: no separate fill pass -- except where chain_layout
+    // chose the memset (fm)
+    m.flag_zero = fm ? 0 : 1;
     // Chunk k runs on lane k % ns (lane 0 = the caller's stream), each lane with its own
     // scratch slot, so PC of one chunk overlaps MTD / CFAR of the previous one.  The lanes
     // fork from and join back into the caller's stream.
@@ -1357,7 +1396,7 @@ static int run_chain_body(rsp_ctx* ctx, const void* d_echo, int32_t dtype, int64
                     }));
                 }
                 pv.nreg = 0;
-            } else if (range_mode() == 1) {   // (dev A/B) the chunk's range stage as its own launch, now
+            } else if (range_per_chunk(L)) {   // (dev A/B) the chunk's range stage as its own launch, now
                 HIP_TRY(ctx, timed(ctx, RSP_K_CFAR_R, ls, [&] {
                     return rsp::launch_cfar_hits(pv.rdm, pv.flag, pv.hits, pv.counts, pv.nreg, pv.reg, cr, ls);
                 }));
@@ -1491,6 +1530,80 @@ int rsp_cfar_dev(rsp_ctx* ctx, const float* d_rdm, int64_t V, int64_t R, int64_t
         HIP_TRY(ctx, timed(ctx, RSP_K_CFAR_R, s, [&] { return rsp::launch_cfar_r(rdm, fv, fl, (int)n, cr, s); }));
     }
     return scratch_release(ctx, s);
+}
+
+int rsp_cfar_plan(rsp_ctx* ctx, int64_t V, int64_t R, int64_t batch, const rsp_cfar_params* cfar, int32_t fused,
+                  int32_t with_rdm, rsp_cfar_plan_t* out) {
+    if (!ctx) return fail(nullptr, RSP_ERR_ARG, "rsp_cfar_plan: null ctx");
+    if (!out || !cfar || V < 1 || R < 1 || batch < 0) return fail(ctx, RSP_ERR_ARG, "rsp_cfar_plan: bad argument");
+    std::memset(out, 0, sizeof(*out));
+    out->fused = fused ? 1 : 0;
+    rsp::CfarRArgs cr;
+    if (!fused) {   // rsp_cfar_dev's checks and launches
+        if ((V + 1) * 4 > 64 * 1024 || R > (1 << 24))
+            return fail(ctx, RSP_ERR_UNSUPPORTED, "rsp_cfar_plan: V=%lld or R=%lld too large", (long long)V, (long long)R);
+        rsp::CfarVArgs cv;
+        int rc = build_cfar(ctx, cfar, V, R, &cv, &cr);
+        if (rc) return rc;
+        if (!rsp::cfar_r_supported(cr))
+            return fail(ctx, RSP_ERR_UNSUPPORTED, "rsp_cfar_plan: a %lld-cell row with range window ref=%d guard=%d "
+                        "needs more than 160 KB of LDS", (long long)R, cr.ref, cr.save);
+        out->v_tile_log2 = rsp::cfar_v_tile_log2((int)V);
+        out->r_kernel = rsp::cfar_r_select(cr, &out->r_groups);
+        return RSP_OK;
+    }
+    // the chain (run_chain_body with win == 0)
+    if (ctx->cfar_only) return fail(ctx, RSP_ERR_ARG, "context was created for CFAR only (params == NULL)");
+    if (V != ctx->V || R != ctx->p.R_out)
+        return fail(ctx, RSP_ERR_SHAPE, "rsp_cfar_plan: %lld x %lld is not the context's %lld x %lld RDM", (long long)V,
+                    (long long)R, (long long)ctx->V, (long long)ctx->p.R_out);
+    rsp::MtdArgs m = ctx->mtd;
+    int rc = build_cfar(ctx, cfar, V, R, &m.cv, &cr);
+    if (rc) return rc;
+    out->window_compiled = rsp::mtd_window_compiled(m) ? 1 : 0;
+    out->bluestein = m.bnf;
+    int W = 0, T = 0;
+    rsp::mtd_geometry((int)V, (int)ctx->beams, &W, &T);
+    out->tile_w = W;
+    out->threads = T;
+    out->region = W * (int32_t)V;
+    if (batch == 0) return RSP_OK;   // the call returns before any launch
+    ChainLayout L;
+    if ((rc = chain_layout(ctx, batch, 0, true, cr, with_rdm != 0, true, &L))) return rc;
+    const rsp::ChunkPlan& plan = L.plan;
+    const int64_t nchunks = plan.nchunks();
+    const int ns = plan.ns;
+    out->region = L.reg;
+    out->nchunks = (int32_t)nchunks;
+    out->nlanes = ns;
+    for (int l = 0; l < ns; ++l) {
+        const int64_t k = l + ns * ((nchunks - 1 - l) / ns);   // the lane's last chunk
+        out->lane_chunk[l] = (int32_t)plan.cap[l];
+        out->lane_last[l] = (int32_t)(plan.cstart[(size_t)k + 1] - plan.cstart[(size_t)k]);
+    }
+    out->flag_memset = L.fm ? 1 : 0;
+    if (!cr.rflag) return RSP_OK;   // RSP_RANGE_NONE, RSP_HITS_NONE
+    // the largest hit-list launch: a lane's last chunk, or (grouped) lane 0's first group
+    int nr = L.nreg[0];
+    if (L.grouped) {
+        const int64_t on0 = (nchunks + ns - 1) / ns;   // chunks on lane 0
+        const int64_t g = on0 < L.rgrp ? on0 : L.rgrp;
+        const int64_t k = ns * (g - 1);
+        int nlast = 0, reg = 0;
+        rsp::mtd_regions((int)V, (int)R, (int)(plan.cstart[(size_t)k + 1] - plan.cstart[(size_t)k]), &nlast, &reg,
+                         (int)ctx->beams);
+        nr = (int)(g - 1) * L.nreg[0] + nlast;
+        out->range_stage = RSP_RANGE_GROUPED;
+    } else if (range_per_chunk(L) || nchunks <= ns) {   // no chunk has a successor on its lane
+        out->range_stage = RSP_RANGE_PER_CHUNK;
+    } else {   // the MTD launch of the lane's next chunk, as run_chain_body hands it over
+        m.prev_nregions = L.nreg[0];
+        m.prev_region = L.reg;
+        m.prev_cr = cr;
+        out->range_stage = rsp::mtd_range_job57(m) ? RSP_RANGE_JOB57 : RSP_RANGE_PREV_HITS;
+    }
+    out->hit_kernel = rsp::cfar_hits_select(cr, nr, L.reg, &out->hit_lanes);
+    return RSP_OK;
 }
 
 // ------------------------------------------------------------------ post-detection measurement

@@ -305,6 +305,19 @@ hipError_t launch_cfar_v(const float* rdm, uint8_t* flagV, int ncpi, int V, int 
 // executeCFAR.m:45-84).  `zero_slot` (if non-null) is reset for a later launch.
 hipError_t launch_cfar_hits(const float* rdm, uint8_t* flag, const uint32_t* hits, const uint32_t* counts,
                             int nregions, int region, const CfarRArgs& a, hipStream_t s);
+// The choices the launchers make, as pure host functions that rsp_cfar_plan reports too:
+// the hit kernel of launch_cfar_hits (RSP_HITS_*; *lpr its lanes per region, 0 for the per-hit kernels)
+int cfar_hits_select(const CfarRArgs& a, int nregions, int region, int* lpr);
+// the range kernel of launch_cfar_r (RSP_CFAR_R_*; *groups its workgroups per row, 0 where one covers a row)
+int cfar_r_select(const CfarRArgs& a, int* groups);
+// log2 of cfar_v_kernel's tile width
+int cfar_v_tile_log2(int V);
+// launch_mtd: the compiled 5 + 7 Doppler window (else the runtime-window instance), and whether the
+// previous chunk's range stage (a.prev_*) rides as RangeJob57 (else as prev_chunk_hits)
+bool mtd_window_compiled(const MtdArgs& a);
+bool mtd_range_job57(const MtdArgs& a);
+// range bins and threads of one MTD workgroup (false: no instance for P / beams)
+bool mtd_geometry(int P, int beams, int* W, int* T);
 // MTD workgroups per launch and cells per workgroup (hit-list regions)
 void mtd_regions(int P, int R_out, int ncpi, int* nregions, int* region, int beams = 1);
 // Bluestein convolution length for a P without a radix plan (0: unsupported)

@@ -1546,6 +1546,17 @@ int mtd_bluestein_nf(int P) {
     return nf <= 2048 ? nf : 0;
 }
 
+// The Doppler stage compiled into mtd_kernel<P, 5, ...> (the reference's 5 + 7 window); any other
+// window runs the runtime-window instance <P, 0, ...>.  Bluestein tiles always take the runtime form.
+bool mtd_window_compiled(const MtdArgs& a) { return a.bnf == 0 && a.cv.enabled && a.cv.ref == 5 && a.cv.save == 7; }
+
+// The in-launch range job (RangeJob57) only in the compiled-window instance and for the reference's
+// range window; any other previous-chunk range stage runs as prev_chunk_hits in the no-job instance.
+bool mtd_range_job57(const MtdArgs& a) {
+    return mtd_window_compiled(a) && a.prev_nregions > 0 && a.prev_cr.ref == 5 && a.prev_cr.save == 7 &&
+           (uint64_t)a.prev_nregions * (uint64_t)a.prev_region < (uint64_t)(kOob / 4u);
+}
+
 template <int P, int REF, int BEAMS>
 static hipError_t launch_mtd_pr(const float2* pc, float* rdm, uint8_t* flagV, int ncpi,
                                 const MtdArgs& a, hipStream_t s) {
@@ -1554,10 +1565,7 @@ static hipError_t launch_mtd_pr(const float2* pc, float* rdm, uint8_t* flagV, in
     static LaunchOnce once, once_job;
     dim3 grid((unsigned)((a.R_out + C::W - 1) / C::W), (unsigned)ncpi),
         block(C::T);
-    // the in-launch range job (RangeJob57) only for the reference's range window; any other
-    // previous-chunk range stage runs as prev_chunk_hits in the no-job instance
-    const bool job = REF > 0 && a.prev_nregions > 0 && a.prev_cr.ref == 5 && a.prev_cr.save == 7 &&
-                     (uint64_t)a.prev_nregions * (uint64_t)a.prev_region < (uint64_t)(kOob / 4u);
+    const bool job = REF > 0 && mtd_range_job57(a);
     if constexpr (REF > 0) {
         if (job) {
             hipError_t e = lds_attr(once_job, (const void*)mtd_kernel<P, REF, BEAMS, true>, lds);
@@ -1582,47 +1590,59 @@ static hipError_t launch_mtd_p(const float2* pc, float* rdm, uint8_t* flagV, int
     if (a.cv.enabled && a.cv.save + a.cv.ref + 2 > C::SPAD) return hipErrorInvalidValue;
     if ((uint64_t)P * a.R_out * 8 >= (uint64_t)kOob) return hipErrorInvalidValue;
     if (a.pin < 1 || a.pin > P || a.beams != BEAMS) return hipErrorInvalidValue;
-    if (a.cv.enabled && a.cv.ref == 5 && a.cv.save == 7) return launch_mtd_pr<P, 5, BEAMS>(pc, rdm, flagV, ncpi, a, s);
+    if (mtd_window_compiled(a)) return launch_mtd_pr<P, 5, BEAMS>(pc, rdm, flagV, ncpi, a, s);
     return launch_mtd_pr<P, 0, BEAMS>(pc, rdm, flagV, ncpi, a, s);
 }
 
-// Hit-list regions of one MTD launch: one per workgroup (tile of W range bins), W * rows
-// entries each -- the tile's own cells, so a region can never overflow.
+// The tile of one MTD workgroup: W range bins by T threads (MtdCfg of the instance launch_mtd runs;
+// Bluestein: of its NF-point transform).  false: no instance for (P, beams).
 template <int P, int BEAMS>
-static void mtd_regions_p(int rows, int R_out, int ncpi, int* nregions, int* region) {
+static void mtd_geometry_p(int* W, int* T) {
     using C = MtdCfg<P, BEAMS>;
-    *nregions = ((R_out + C::W - 1) / C::W) * ncpi;
-    *region = C::W * rows;
+    *W = C::W;
+    *T = C::T;
 }
 
-void mtd_regions(int P, int R_out, int ncpi, int* nregions, int* region, int beams) {
-    *nregions = 0;
-    *region = 0;
+bool mtd_geometry(int P, int beams, int* W, int* T) {
+    *W = 0;
+    *T = 0;
     if (beams == 1 && !mtd_size_supported(P, 1)) {   // Bluestein: NF-point tiles, P rows kept
         switch (mtd_bluestein_nf(P)) {
-#define RSP_MB(nf) case nf: mtd_regions_p<nf, 1>(P, R_out, ncpi, nregions, region); break;
+#define RSP_MB(nf) case nf: mtd_geometry_p<nf, 1>(W, T); break;
             RSP_MB(64) RSP_MB(128) RSP_MB(256) RSP_MB(512) RSP_MB(1024) RSP_MB(2048)
 #undef RSP_MB
             default: break;
         }
-        return;
+        return *W > 0;
     }
     if (beams == 2) {
         switch (P) {
-            case 512: mtd_regions_p<512, 2>(P, R_out, ncpi, nregions, region); break;
-            case 1024: mtd_regions_p<1024, 2>(P, R_out, ncpi, nregions, region); break;
-            case 2048: mtd_regions_p<2048, 2>(P, R_out, ncpi, nregions, region); break;
+            case 512: mtd_geometry_p<512, 2>(W, T); break;
+            case 1024: mtd_geometry_p<1024, 2>(W, T); break;
+            case 2048: mtd_geometry_p<2048, 2>(W, T); break;
             default: break;
         }
-        return;
+        return *W > 0;
     }
     switch (P) {
-#define RSP_MR(p) case p: mtd_regions_p<p, 1>(P, R_out, ncpi, nregions, region); break;
+#define RSP_MR(p) case p: mtd_geometry_p<p, 1>(W, T); break;
         RSP_MR(16) RSP_MR(32) RSP_MR(64) RSP_MR(128) RSP_MR(256) RSP_MR(512) RSP_MR(1024)
         RSP_MR(2048) RSP_MR(48) RSP_MR(96) RSP_MR(192) RSP_MR(384) RSP_MR(768) RSP_MR(1536)
 #undef RSP_MR
         default: break;
     }
+    return *W > 0;
+}
+
+// Hit-list regions of one MTD launch: one per workgroup (tile of W range bins), W * P
+// entries each -- the tile's own cells, so a region can never overflow.
+void mtd_regions(int P, int R_out, int ncpi, int* nregions, int* region, int beams) {
+    *nregions = 0;
+    *region = 0;
+    int W = 0, T = 0;
+    if (!mtd_geometry(P, beams, &W, &T)) return;
+    *nregions = ((R_out + W - 1) / W) * ncpi;
+    *region = W * P;
 }
 
 bool mtd_size_supported(int P, int beams) {
@@ -1711,11 +1731,18 @@ __global__ __launch_bounds__(kBlock) void cfar_v_kernel(const float* __restrict_
     doppler_flags(mag, sums, cv, col_on, v0, v1, flagV + cpi * (size_t)V * R + r, R, rv);
 }
 
+// log2 of the tile width: the widest of 64, 32, ... columns whose two V + 1 float columns per
+// range bin fit 96 KB of LDS.
+int cfar_v_tile_log2(int V) {
+    int lw = 6;
+    while (lw > 0 && (size_t)2 * (1 << lw) * (V + 1) * sizeof(float) > 96 * 1024) --lw;
+    return lw;
+}
+
 hipError_t launch_cfar_v(const float* rdm, uint8_t* flagV, int ncpi, int V, int R,
                          const CfarVArgs& a, hipStream_t s) {
     if (ncpi <= 0) return hipSuccess;
-    int lw = 6;
-    while (lw > 0 && (size_t)2 * (1 << lw) * (V + 1) * sizeof(float) > 96 * 1024) --lw;
+    const int lw = cfar_v_tile_log2(V);
     const size_t lds = (size_t)2 * (1 << lw) * (V + 1) * sizeof(float);
     static LaunchOnce once;
     hipError_t e = lds_attr(once, (const void*)cfar_v_kernel, 160 * 1024);
@@ -2077,21 +2104,40 @@ static bool hits_big() {
     return b;
 }
 
-hipError_t launch_cfar_hits(const float* rdm, uint8_t* flag, const uint32_t* hits, const uint32_t* counts,
-                            int nregions, int region, const CfarRArgs& a, hipStream_t s) {
-    if (nregions <= 0) return hipSuccess;
-    // (the chunk's RDM holds nregions * region cells: byte offsets stay below the range check).
-    // Hits per region grow with the tile's pulse count: regions of up to 4096 cells (c3: ~10
-    // hits, c4: ~50) take a wave each (c4: 44 -> 31 us per launch, c3 unchanged); the 8192-cell
-    // regions of P = 512 (c5: ~460 hits) keep a workgroup each (a wave took 12 -> 22 us).
-    if (a.ref == 5 && a.save == 7 && region >= 64 && region <= 4096 &&
-        (uint64_t)nregions * (uint64_t)region < (uint64_t)(kOob / 4u)) {
+// The kernel launch_cfar_hits runs for a list of nregions regions of `region` cells (RSP_HITS_*,
+// rsp.h); *lpr: the lanes per region of the batched 5 + 7 kernel, else 0.
+// (The chunk's RDM holds nregions * region cells: byte offsets stay below the range check.)
+// Hits per region grow with the tile's pulse count: regions of up to 4096 cells (c3: ~10
+// hits, c4: ~50) take a wave each (c4: 44 -> 31 us per launch, c3 unchanged); the 8192-cell
+// regions of P = 512 (c5: ~460 hits) keep a workgroup each (a wave took 12 -> 22 us).
+int cfar_hits_select(const CfarRArgs& a, int nregions, int region, int* lpr) {
+    *lpr = 0;
+    const bool w57 = a.ref == 5 && a.save == 7;
+    const bool fits = (uint64_t)nregions * (uint64_t)region < (uint64_t)(kOob / 4u);
+    if (w57 && region >= 64 && region <= 4096 && fits) {
         // lanes per region: 16 for the sparse hit lists of tiles of <= 128 Doppler rows (c3: ~11
         // hits per region, range stage 37.5 -> 29.2 us per 16-chunk group, c3 +1.3 %), a wave for
         // longer tiles (c4: ~50 hits, 46.6 us at 64 lanes against 50.1 at 32 and 56.0 at 16;
         // profiles/r05/ab/range_stage_grouping.txt).  Dev A/B: environment RSP_HITS_LPR.
         static const int lpr_env = [] { const char* v = getenv("RSP_HITS_LPR"); return v && *v ? atoi(v) : 0; }();
-        const int lpr = lpr_env > 0 ? lpr_env : (a.V <= 128 ? 16 : 64);
+        const int l = lpr_env > 0 ? lpr_env : (a.V <= 128 ? 16 : 64);
+        *lpr = l == 16 ? 16 : l == 32 ? 32 : 64;
+        return RSP_HITS_BATCHED57;
+    }
+    if (w57 && region >= kHitThreads && hits_big() && fits) {
+        // larger regions: the batched gathers with the whole workgroup on a region
+        *lpr = kHitThreads;
+        return RSP_HITS_BATCHED57;
+    }
+    return w57 ? RSP_HITS_PER_HIT57 : RSP_HITS_PER_HIT_RUNTIME;   // the reference's parameters / any window
+}
+
+hipError_t launch_cfar_hits(const float* rdm, uint8_t* flag, const uint32_t* hits, const uint32_t* counts,
+                            int nregions, int region, const CfarRArgs& a, hipStream_t s) {
+    if (nregions <= 0) return hipSuccess;
+    int lpr = 0;
+    const int kind = cfar_hits_select(a, nregions, region, &lpr);
+    if (kind == RSP_HITS_BATCHED57 && lpr < kHitThreads) {
         auto go = [&](auto kern, int rpw) {
             const int rpb = (kHitThreads / 64) * rpw;   // regions per workgroup
             hipLaunchKernelGGL(kern, dim3((unsigned)((nregions + rpb - 1) / rpb)), dim3(kHitThreads), 0, s, rdm, flag,
@@ -2100,12 +2146,10 @@ hipError_t launch_cfar_hits(const float* rdm, uint8_t* flag, const uint32_t* hit
         if (lpr == 16) go(cfar_hits57_kernel<16>, 4);
         else if (lpr == 32) go(cfar_hits57_kernel<32>, 2);
         else go(cfar_hits57_kernel<64>, 1);
-    } else if (a.ref == 5 && a.save == 7 && region >= kHitThreads && hits_big() &&
-               (uint64_t)nregions * (uint64_t)region < (uint64_t)(kOob / 4u)) {
-        // larger regions: the batched gathers with the whole workgroup on a region
+    } else if (kind == RSP_HITS_BATCHED57) {
         hipLaunchKernelGGL(cfar_hits57_kernel<kHitThreads>, dim3((unsigned)nregions), dim3(kHitThreads), 0, s, rdm, flag,
                            hits, counts, nregions, region, a);
-    } else if (a.ref == 5 && a.save == 7)   // the reference's parameters
+    } else if (kind == RSP_HITS_PER_HIT57)
         hipLaunchKernelGGL((cfar_hits_kernel<5, 7>), dim3((unsigned)nregions), dim3(kHitThreads), 0, s, rdm, flag,
                            hits, counts, nregions, region, a);
     else
@@ -2122,6 +2166,21 @@ static size_t cfar_r_generic_lds(const CfarRArgs& a) {
 }
 bool cfar_r_supported(const CfarRArgs& a) { return cfar_r_specialised(a) || cfar_r_generic_lds(a) <= 160 * 1024; }
 
+// The kernel launch_cfar_r runs (RSP_CFAR_R_*, rsp.h); *groups: workgroups per row of the
+// window-specialised kernels (16 or 4 cells per thread), 0 for the one-workgroup-per-row kernel.
+int cfar_r_select(const CfarRArgs& a, int* groups) {
+    *groups = 0;
+    if (cfar_r_specialised(a) && (a.R & 15) == 0) {
+        *groups = (a.R / 16 + kBlock - 1) / kBlock;
+        return RSP_CFAR_R_16CELL;
+    }
+    if (cfar_r_specialised(a)) {
+        *groups = (a.R / 4 + kBlock - 1) / kBlock;
+        return RSP_CFAR_R_4CELL;
+    }
+    return a.rflag ? RSP_CFAR_R_GENERIC : RSP_CFAR_R_COPY;   // (the copy is the generic kernel's rflag == 0 branch)
+}
+
 hipError_t launch_cfar_r(const float* rdm, const uint8_t* flagV, uint8_t* flag, int ncpi,
                          const CfarRArgs& a, hipStream_t s) {
     if (ncpi <= 0) return hipSuccess;
@@ -2130,14 +2189,14 @@ hipError_t launch_cfar_r(const float* rdm, const uint8_t* flagV, uint8_t* flag, 
     static LaunchOnce once;
     hipError_t e = lds_attr(once, (const void*)cfar_r_generic_kernel, 160 * 1024);
     if (e != hipSuccess) return e;
-    if (a.ref == 5 && a.save == 7 && a.rflag && (a.R & 15) == 0) {   // the reference's parameters
-        const int groups = (a.R / 16 + kBlock - 1) / kBlock;
+    int groups = 0;
+    const int kind = cfar_r_select(a, &groups);
+    if (kind == RSP_CFAR_R_16CELL) {   // the reference's parameters
         dim3 grid((unsigned)(groups * a.V), (unsigned)ncpi), block(kBlock);
         hipLaunchKernelGGL((cfar_r16_kernel<5, 7>), grid, block, 0, s, rdm, flagV, flag, a, groups);
         return hipGetLastError();
     }
-    if (a.ref == 5 && a.save == 7 && a.rflag && (a.R & 3) == 0) {
-        const int groups = (a.R / 4 + kBlock - 1) / kBlock;
+    if (kind == RSP_CFAR_R_4CELL) {
         dim3 grid((unsigned)(groups * a.V), (unsigned)ncpi), block(kBlock);
         hipLaunchKernelGGL((cfar_r_kernel<5, 7>), grid, block, 0, s, rdm, flagV, flag, a, groups);
         return hipGetLastError();

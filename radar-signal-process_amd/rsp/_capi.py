@@ -32,7 +32,8 @@ EXPORTS = ("rsp_version", "rsp_create", "rsp_destroy", "rsp_last_error", "rsp_se
            "rsp_mtd_cfar_dev", "rsp_set_pc_split", "rsp_set_host_pipeline", "rsp_ingest_record_bytes",
            "rsp_ingest_ddc_dev", "rsp_ingest_frame_dev", "rsp_motion_measure_dev", "rsp_prefilter_dev", "rsp_set_prefilter",
            "rsp_pc_mtd_cfar_f64", "rsp_cfar_f64", "rsp_set_range_concat", "rsp_score_dev", "rsp_score_summary",
-           "rsp_set_pc_prune", "rsp_set_lane_chunks", "rsp_pc_plan", "rsp_scr_dev", "rsp_inject_dev", "rsp_scr_gain")
+           "rsp_set_pc_prune", "rsp_set_lane_chunks", "rsp_pc_plan", "rsp_scr_dev", "rsp_inject_dev", "rsp_scr_gain",
+           "rsp_cfar_plan")
 RSP_NKERNELS = 4
 KERNEL_NAMES = ("pc_kernel", "mtd_kernel", "cfar_r_kernel", "cfar_v_kernel")
 
@@ -100,6 +101,20 @@ class rsp_pc_plan_seg(C.Structure):
 class rsp_pc_plan_t(C.Structure):
     _fields_ = [("specialised", C.c_int32), ("fused", C.c_int32), ("prune", C.c_int32), ("nmf", C.c_int32),
                 ("seg", rsp_pc_plan_seg * RSP_MAX_SEG)]
+
+
+class rsp_cfar_plan_t(C.Structure):
+    _fields_ = [("fused", C.c_int32), ("v_tile_log2", C.c_int32), ("r_kernel", C.c_int32), ("r_groups", C.c_int32),
+                ("window_compiled", C.c_int32), ("bluestein", C.c_int32), ("tile_w", C.c_int32),
+                ("threads", C.c_int32), ("region", C.c_int32), ("nchunks", C.c_int32), ("nlanes", C.c_int32),
+                ("lane_chunk", C.c_int32 * 4), ("lane_last", C.c_int32 * 4), ("range_stage", C.c_int32),
+                ("hit_kernel", C.c_int32), ("hit_lanes", C.c_int32), ("flag_memset", C.c_int32)]
+
+
+# rsp_cfar_plan_t.r_kernel / .range_stage / .hit_kernel
+RSP_CFAR_R_COPY, RSP_CFAR_R_GENERIC, RSP_CFAR_R_4CELL, RSP_CFAR_R_16CELL = range(4)
+RSP_RANGE_NONE, RSP_RANGE_GROUPED, RSP_RANGE_JOB57, RSP_RANGE_PREV_HITS, RSP_RANGE_PER_CHUNK = range(5)
+RSP_HITS_NONE, RSP_HITS_BATCHED57, RSP_HITS_PER_HIT57, RSP_HITS_PER_HIT_RUNTIME = range(4)
 
 
 class rsp_scr_params(C.Structure):
@@ -181,6 +196,8 @@ def load_library(path=None):
     lib.rsp_set_pc_prune.argtypes = [vp, i32]
     lib.rsp_pc_plan.restype = C.c_int
     lib.rsp_pc_plan.argtypes = [vp, C.POINTER(rsp_pc_plan_t), i32]
+    lib.rsp_cfar_plan.restype = C.c_int
+    lib.rsp_cfar_plan.argtypes = [vp, i64, i64, i64, C.POINTER(rsp_cfar_params), i32, i32, C.POINTER(rsp_cfar_plan_t)]
     lib.rsp_set_lane_chunks.restype = C.c_int
     lib.rsp_set_lane_chunks.argtypes = [vp, C.POINTER(i64), i32]
     lib.rsp_set_host_pipeline.restype = C.c_int

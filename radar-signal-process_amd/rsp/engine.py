@@ -96,6 +96,30 @@ class Engine:
         segs = [(g.nfft, g.nsub, g.sub_step, g.zin, g.zout, g.fir) for g in p.seg[:p.nmf]]
         return dict(specialised=p.specialised, fused=p.fused, prune=p.prune, segs=segs)
 
+    def cfar_plan(self, cfar, batch, V=None, R=None, fused=None, rdm=True):
+        """The CFAR kernels a call would run (rsp_cfar_plan), as a dict of the fields that apply.
+        fused=False: cfar_dev / cfar on [batch, V, R] -- v_tile_log2, r_kernel, r_groups.
+        fused=True (the default on a chain context; V and R are the spec's): mtd_dev / run_dev on
+        `batch` CPIs with (rdm=True) or without an RDM output -- window_compiled, bluestein, tile_w,
+        threads, region, nchunks, nlanes, lane_chunk and lane_last (one entry per pipeline in use),
+        range_stage, hit_kernel, hit_lanes, flag_memset.  The codes are capi.RSP_CFAR_R_*,
+        RSP_RANGE_* and RSP_HITS_*."""
+        if fused is None:
+            fused = self.spec is not None
+        if fused:
+            V, R = self.spec.V, self.spec.R_out
+        p = capi.rsp_cfar_plan_t()
+        cp = cfar.to_c()
+        capi.check(self.lib.rsp_cfar_plan(self.ctx, int(V), int(R), int(batch), C.byref(cp), int(bool(fused)),
+                                          int(bool(rdm)), C.byref(p)), self.ctx)
+        if not fused:
+            return dict(fused=0, v_tile_log2=p.v_tile_log2, r_kernel=p.r_kernel, r_groups=p.r_groups)
+        n = p.nlanes
+        return dict(fused=1, window_compiled=p.window_compiled, bluestein=p.bluestein, tile_w=p.tile_w,
+                    threads=p.threads, region=p.region, nchunks=p.nchunks, nlanes=n,
+                    lane_chunk=list(p.lane_chunk[:n]), lane_last=list(p.lane_last[:n]), range_stage=p.range_stage,
+                    hit_kernel=p.hit_kernel, hit_lanes=p.hit_lanes, flag_memset=p.flag_memset)
+
     def set_host_pipeline(self, cpis_per_chunk=0, copy_threads=0):
         """Host-buffer calls (pc_mtd_cfar / pc_mtd): CPIs per pipelined chunk and host copy
         threads (0 = the library defaults) -- rsp_set_host_pipeline."""

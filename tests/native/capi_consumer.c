@@ -15,6 +15,7 @@
  *     the full RDM's columns gathered, bit for bit; a part past the width is RSP_ERR_ARG; 0 parts
  *     restore the full width;
  *   - rsp_pc_plan: the pulse-compression launches of this shape (the fused, pruned 1024/4096 pair);
+ *   - rsp_cfar_plan: the CFAR kernels behind the chain call and behind rsp_cfar on the same shape;
  *   - the error contract: a wrong shape is RSP_ERR_SHAPE with a message, a null context
  *     RSP_ERR_ARG.
  * Prints "ok <peak row> <peak column> <detections>" and exits 0, or prints the failed check
@@ -95,6 +96,36 @@ int main(void) {
                                plan.seg[1].nsub == 0 && plan.seg[1].zin == 3 && plan.seg[1].zout == 3),
               "rsp_pc_plan: specialised %d fused %d prune 0x%x, %d segments", plan.specialised, plan.fused,
               (unsigned)plan.prune, plan.nmf);
+    }
+    {   /* ... and the CFAR behind it: the 5 + 7 Doppler window compiled into the 32-bin, 256-thread MTD
+           tiles of P = 128, one chunk on one pipeline, its 128 hit-list regions of 4096 cells read by
+           one grouped launch of the batched kernel at 16 lanes per region (V <= 128) */
+        rsp_cfar_plan_t cp;
+        memset(&cp, 0xff, sizeof(cp));
+        rc = rsp_cfar_plan(ctx, P, R, 1, &cf, 1, 1, &cp);
+        CHECK(rc == RSP_OK, "rsp_cfar_plan: %d %s", rc, rsp_last_error(ctx));
+        CHECK(rc != RSP_OK || (cp.fused == 1 && cp.window_compiled == 1 && cp.bluestein == 0 && cp.tile_w == 32 &&
+                               cp.threads == 256 && cp.region == 4096 && cp.nchunks == 1 && cp.nlanes == 1 &&
+                               cp.lane_chunk[0] == 1 && cp.lane_last[0] == 1 && cp.lane_chunk[1] == 0 &&
+                               cp.range_stage == RSP_RANGE_GROUPED && cp.hit_kernel == RSP_HITS_BATCHED57 &&
+                               cp.hit_lanes == 16 && cp.flag_memset == 0 && cp.r_kernel == 0 && cp.v_tile_log2 == 0),
+              "rsp_cfar_plan: window %d tile %d x %d region %d chunks %d lanes %d stage %d kernel %d lanes %d",
+              cp.window_compiled, cp.tile_w, cp.threads, cp.region, cp.nchunks, cp.nlanes, cp.range_stage,
+              cp.hit_kernel, cp.hit_lanes);
+        /* the stand-alone call on the same shape: 64-column Doppler tiles, the 16-cell range kernel
+           with one workgroup per 4096-cell row; a window the kernels were not built for is refused
+           as the call itself refuses it */
+        rc = rsp_cfar_plan(ctx, P, R, 1, &cf, 0, 0, &cp);
+        CHECK(rc == RSP_OK && cp.fused == 0 && cp.v_tile_log2 == 6 && cp.r_kernel == RSP_CFAR_R_16CELL &&
+                  cp.r_groups == 1 && cp.tile_w == 0,
+              "rsp_cfar_plan (stand-alone): %d tile 2^%d kernel %d groups %d", rc, cp.v_tile_log2, cp.r_kernel,
+              cp.r_groups);
+        rsp_cfar_params big = cf;
+        big.refR = 17; big.saveR = 14;
+        rc = rsp_cfar_plan(ctx, P, R, 1, &big, 0, 0, &cp);
+        CHECK(rc == RSP_ERR_UNSUPPORTED, "rsp_cfar_plan with a 17 + 14 range window: status %d", rc);
+        rc = rsp_cfar_plan(ctx, P + 1, R, 1, &cf, 1, 1, &cp);
+        CHECK(rc == RSP_ERR_SHAPE, "rsp_cfar_plan for another shape than the context's: status %d", rc);
     }
     rc = rsp_pc_mtd_cfar(ctx, col, RSP_C128, RSP_COLMAJOR, P, R, 1, &cf, rdm_c, RSP_COLMAJOR, fl_c, fv_c);
     CHECK(rc == RSP_OK, "rsp_pc_mtd_cfar column-major: %d %s", rc, rsp_last_error(ctx));

@@ -1,7 +1,7 @@
 """The MEX shims executed: each radar-signal-process_amd/mex/*.c linked with a fake MEX runtime
-(tests/mex_stub/mex_runtime.c, built by __graft_entry__.build()) and called the way MATLAB
-calls it -- column-major complex/real double arrays and a params struct in, double arrays
-out, mexErrMsgIdAndTxt unwinding.  CPU tests exercise argument checking (no device call);
+(tests/mex_stub/mex_runtime.c, built by __graft_entry__.build(), or by Mex() below where the
+libraries are missing) and called the way MATLAB calls it -- column-major complex/real double
+arrays and a params struct in, double arrays out, mexErrMsgIdAndTxt unwinding.  CPU tests exercise argument checking (no device call);
 the -m gpu tests compare the shims' outputs with the fp64 oracle (chain bars: RDM rel-err
 <= 1e-5, flags equal outside the near-threshold band).
 
@@ -10,6 +10,7 @@ drop-ins INTEGRATION.md §1 describes (MTD/fun_MTD_produce.m:12,
 MatlabProcess_xuzerui/fun_MTD_produce.m:3, CFAR_WangCai/executeCFAR.m:1-2)."""
 import ctypes as C
 import os
+import subprocess
 
 import numpy as np
 import pytest
@@ -25,6 +26,8 @@ class Mex:
 
     def __init__(self, name):
         path = os.path.join(BUILD, "lib%s_mex.so" % name)
+        if not os.path.exists(path):   # a tree whose tests/ lost its build products: two small C files
+            subprocess.run(["make", "-s", "-C", os.path.dirname(BUILD)], capture_output=True)
         if not os.path.exists(path):
             pytest.skip("%s not built (run __graft_entry__.build())" % path)
         os.environ.setdefault("RSP_DATA_DIR", DATA)
