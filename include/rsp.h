@@ -116,7 +116,11 @@ typedef struct {
 } rsp_pc_segment;
 
 typedef struct {
-    int64_t P;             /* pulses per CPI: 2^k or 3*2^k, 16 <= P <= 1536 */
+    int64_t P;             /* pulses per CPI, P >= 2.  The Doppler length V (mtd_nfft, or P) must be
+                              a radix length -- 2^k, 16..2048, or 3*2^k, 48..1536 -- with any
+                              P <= V; on one beam with mtd_nfft = 0 every other 2 <= P <= 1024 runs
+                              by Bluestein.  Two beams: V = 512, 1024 or 2048.  Anything else:
+                              RSP_ERR_UNSUPPORTED */
     int64_t R;             /* input range bins per pulse */
     int64_t R_out;         /* output range bins (PC output = RDM columns) */
     int32_t nseg;          /* pulse-compression segments (<= RSP_MAX_SEG) */

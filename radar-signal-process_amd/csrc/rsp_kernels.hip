@@ -1479,13 +1479,14 @@ __global__ __launch_bounds__(MtdCfg<NF>::T) void mtd_bluestein_kernel(const floa
     const auto dst = buf_rsrc(rdm + cpi * plane, plane * 4u);
     float mg[E];
     int vr[E];
+    const int zw = a.z_hi > P ? a.z_hi - P : 0;   // the zero_ends band wraps through row 0, as in mtd_tile
 #pragma unroll
     for (int m = 0; m < E; ++m) {
         const int k = g + G * m;                   // Doppler bin
         int v = k + a.shift;                       // fftshift: out[v] = X[(v - shift) mod P]
         if (v >= P) v -= P;
         float x = __builtin_amdgcn_sqrtf(fmaf(u[m].x, u[m].x, u[m].y * u[m].y));
-        if (v >= a.z_lo && v < a.z_hi) x = 0.f;   // fun_0v_pressing
+        if ((v >= a.z_lo && v < a.z_hi) || v < zw) x = 0.f;   // fun_0v_pressing / zero_ends
         mg[m] = x;
         vr[m] = k < P ? v : -1;
         if (k < P) buf_st_f(x, dst, rv ? ((uint32_t)v * R + (uint32_t)r) * 4u : kOob, 0u);
