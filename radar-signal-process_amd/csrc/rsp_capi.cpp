@@ -8,8 +8,6 @@
 // the fast-time (PC) and slow-time (MTD) passes is served on-die instead of from HBM.
 #include <hip/hip_runtime.h>
 
-#include <atomic>
-#include <chrono>
 #include <cmath>
 #include <complex>
 #include <cstdarg>
@@ -17,118 +15,17 @@
 #include <cstdlib>
 #include <cstring>
 #include <map>
-#include <memory>
-#include <exception>
 #include <new>
 #include <string>
-#include <thread>
 #include <vector>
 
-#include "../../include/rsp.h"
-#include "rsp_hostpool.h"
-#include "rsp_chunkplan.h"
-#include "rsp_internal.h"
+#include "rsp_ctx.h"
 
 using cd = std::complex<double>;
 
-struct DevBuf {
-    void* p = nullptr;
-    size_t n = 0;
-};
-
-struct rsp_ctx {
-    int device = 0;
-    bool cfar_only = false;   // created with params == NULL
-    rsp_params p{};
-    std::string err;
-    hipStream_t stream = nullptr;
-    rsp::PcArgs pc{};
-    bool pc_v2 = false;                 // per-segment specialised kernels (pc_mf_kernel)
-#ifndef RSP_PC_OLS_MIN
-// 4096: an 8192-point segment (c4) runs as 3 blocks of 4096 points at four workgroups per CU
-// instead of one whole-row transform at two: PC 289-301 -> 275-282 us per c4 step, chain +1.2-2.3 %
-// (profiles/r04/ab/session9_ols4k.txt; dev-only -D for A/B of the threshold)
-#define RSP_PC_OLS_MIN 4096
-#endif
-    int pc_ols_min = RSP_PC_OLS_MIN;    // overlap-save split of segments longer than this
-    std::vector<rsp::PcMfArgs> pc_mf_whole, pc_mf_split;   // per MF segment, for rsp_set_pc_split
-    std::vector<rsp::PcMfArgs> pc_mf;   // one launch per matched-filter segment
-    int64_t lane_cpis[rsp::kMaxLanes] = {};   // rsp_set_lane_chunks: per-pipeline chunk sizes
-    int nlane_cpis = 0;                       // 0: equal chunks / the default split
-    // rsp_set_pc_prune: pruned PC kernel instances where built (dev A/B: RSP_PC_PRUNE=0 starts off)
-    bool pc_prune = [] { const char* v = getenv("RSP_PC_PRUNE"); return !(v && *v == '0'); }();
-    rsp::MtdArgs mtd{};
-    int64_t V = 0;                      // Doppler rows (rsp_params.mtd_nfft or P)
-    int beams = 1;                      // 2: DMX left/right pair
-    size_t pc_lds = 0;
-    int64_t chunk = 0;  // 0 = default
-    int nstreams = 0;   // chunk pipelines (the caller's stream + nstreams-1 internal ones); 0 = default
-    hipStream_t aux[3] = {nullptr, nullptr, nullptr};
-    hipEvent_t ev_fork = nullptr, ev_join[3] = {nullptr, nullptr, nullptr};
-    // The context's scratch (PC corner turn, hit lists, internal RDM, flagV staging) is reused by
-    // every _dev call: a call's stream waits for the previous call's release event first, so
-    // calls on different streams never overlap on it.
-    hipEvent_t ev_scratch = nullptr;
-    bool scratch_pending = false;
-    std::vector<void*> owned;           // constant tables (freed at destroy)
-    std::map<int, float2*> tw;          // twiddle tables by length
-    DevBuf scratch_pc, tmp_flagV, tmp_rdm;
-    // range concatenation between PC and MTD (rsp_set_range_concat, fun_lss_range_concate):
-    // PC rows are pc_w wide (the params' R_out); the MTD and every output see p.R_out = the sum
-    // of the ncat parts; cat_tmp holds the full-width PC rows of each pipeline
-    int64_t pc_w = 0;
-    int ncat = 0;
-    int64_t cat_src[RSP_MAX_SEG] = {}, cat_len[RSP_MAX_SEG] = {};
-    DevBuf cat_tmp;
-    DevBuf pf_gain;                     // fused iSTC gains (rsp_set_prefilter)
-    DevBuf hit_list;                    // per-lane Doppler-hit lists (fused range CFAR)
-    DevBuf hit_ctr;                     // per-lane, per-MTD-workgroup hit counts
-    DevBuf meas_band;                   // measurement: per-(CPI, band, column) hit counts
-    DevBuf scr_ps;                      // injection: per-CPI sums, ratios and pulse phases (InjectArgs::ps)
-    DevBuf ing_meta;                    // ingest: per-PRT record offsets and types
-    DevBuf st_in, st_canon, st_rdm, st_flag, st_flagV, st_t;  // host-API staging (rsp_cfar)
-    // Pipelined host-buffer path (rsp_pc_mtd_cfar / rsp_pc_mtd): chunk k's H2D (copy stream),
-    // chain (ctx->stream) and D2H (copy stream) overlap chunks k+1 and k-1; pageable <-> pinned
-    // staging through rings of pinned pieces, copied by a host thread pool.
-    struct HostPipe {
-        static constexpr int kSlots = 2;      // chunk slots (device buffers)
-        static constexpr int kRing = 4;       // pinned pieces per direction
-        hipStream_t s_h2d = nullptr, s_d2h = nullptr;
-        DevBuf in[kSlots], canon[kSlots], rdm[kSlots], flag[kSlots], flagV[kSlots], tr[kSlots][3];
-        hipEvent_t ev_in[kSlots] = {}, ev_comp[kSlots] = {}, ev_out[kSlots] = {};
-        void* pin_in[kRing] = {};
-        void* pin_out[kRing] = {};
-        hipEvent_t ev_pin_in[kRing] = {}, ev_pin_out[kRing] = {};
-        size_t piece = 0;                     // bytes per pinned piece
-        int ring_in = 0;                      // next input piece slot
-        int threads = 0;                      // requested copy threads (0 = default)
-        std::unique_ptr<rsp::CopyPool> pool;
-        std::unique_ptr<rsp::Prefaulter> prefault;   // fresh output arrays (host_prefault)
-        rsp::Prefaulter* pf = nullptr;                // the running call's prefault job, if any
-        // one-chunk calls (host_chain_small): pinned staging the kernels read and write directly
-        static constexpr int kParts = 16;     // output parts in flight (one event each)
-        void* zc_in = nullptr;
-        void* zc_out = nullptr;
-        size_t zc_in_n = 0, zc_out_n = 0;
-        hipEvent_t ev_part[kParts] = {};
-    } hp;
-    int64_t host_chunk = 0;                   // CPIs per host chunk (0 = by bytes)
-    // diagnostics (rsp_profile): HIP event pairs around each kernel launch
-    struct Ev {
-        int k;
-        hipEvent_t a, b;
-    };
-    int prof = 0;            // 0 off; N >= 1: bracket every N-th launch
-    uint64_t prof_tick = 0;
-    std::vector<Ev> evs;
-    size_t nev = 0;
-    double prof_ms[RSP_NKERNELS] = {};
-    int64_t prof_n[RSP_NKERNELS] = {};
-};
-
 static thread_local std::string g_err;
 
-static int fail(rsp_ctx* ctx, int code, const char* fmt, ...) {
+int fail(rsp_ctx* ctx, int code, const char* fmt, ...) {
     char buf[512];
     va_list ap;
     va_start(ap, fmt);
@@ -139,13 +36,6 @@ static int fail(rsp_ctx* ctx, int code, const char* fmt, ...) {
     return code;
 }
 
-#define HIP_TRY(ctx, expr)                                                                   \
-    do {                                                                                     \
-        hipError_t e_ = (expr);                                                              \
-        if (e_ != hipSuccess)                                                                \
-            return fail((ctx), RSP_ERR_HIP, "%s: %s (%s:%d)", #expr, hipGetErrorString(e_),   \
-                        __FILE__, __LINE__);                                                 \
-    } while (0)
 
 // ------------------------------------------------------------------ host numerics (fp64)
 static double mround(double x) { return x >= 0 ? std::floor(x + 0.5) : -std::floor(-x + 0.5); }
@@ -292,7 +182,7 @@ static void pc_prune_counts(rsp::PcMfArgs& a) {
     a.zout = (n - out) / g;
 }
 
-static int ensure(rsp_ctx* ctx, DevBuf& b, size_t bytes) {
+int ensure(rsp_ctx* ctx, DevBuf& b, size_t bytes) {
     if (b.n >= bytes && b.p) return RSP_OK;
     if (b.p) {
         HIP_TRY(ctx, hipFree(b.p));
@@ -787,7 +677,7 @@ static void default_lane_split(int64_t cu, int64_t* a, int64_t* b) {
 }
 
 
-static bool set_device(rsp_ctx* ctx) { return hipSetDevice(ctx->device) == hipSuccess; }
+bool set_device(rsp_ctx* ctx) { return hipSetDevice(ctx->device) == hipSuccess; }
 
 static int64_t chunk_of(const rsp_ctx* ctx, int64_t batch) {
     int64_t c = ctx->chunk;
@@ -1976,792 +1866,3 @@ int rsp_ingest_frame_dev(rsp_ctx* ctx, const uint8_t* d_stream, int64_t nbytes, 
     return ingest_run(ctx, "rsp_ingest_frame_dev", false, d_stream, nbytes, p, d_dbf, d_out, beam_stride, d_servo,
                       d_status, stream);
 }
-
-// ------------------------------------------------------------------ host-buffer entry points
-static size_t dtype_size(int32_t dtype) {
-    switch (dtype) {
-        case RSP_C64: return 8;
-        case RSP_C128: return 16;
-        case RSP_C32F16: return 4;
-        default: return 0;
-    }
-}
-
-template <typename T>
-static int fetch(rsp_ctx* ctx, const T* d, T* h, int64_t batch, int64_t A, int64_t B, int32_t layout) {
-    const size_t n = (size_t)batch * A * B;
-    if (layout == RSP_COLMAJOR) {
-        int rc = ensure(ctx, ctx->st_t, n * sizeof(T));
-        if (rc) return rc;
-        hipError_t e;
-        if (sizeof(T) == 4)
-            e = rsp::launch_transpose_f32((const float*)d, (float*)ctx->st_t.p, batch, (int)A, (int)B, ctx->stream);
-        else
-            e = rsp::launch_transpose_u8((const uint8_t*)d, (uint8_t*)ctx->st_t.p, batch, (int)A, (int)B, ctx->stream);
-        HIP_TRY(ctx, e);
-        d = (const T*)ctx->st_t.p;
-    }
-    HIP_TRY(ctx, hipMemcpyAsync(h, d, n * sizeof(T), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return RSP_OK;
-}
-
-static int check_host_call(rsp_ctx* ctx, const void* echo, int32_t dtype, int32_t layout, int64_t P,
-                           int64_t R, int64_t batch) {
-    if (ctx->cfar_only) return fail(ctx, RSP_ERR_ARG, "context was created for CFAR only (params == NULL)");
-    if (!echo || batch < 0) return fail(ctx, RSP_ERR_ARG, "null echo or negative batch");
-    if (!dtype_size(dtype)) return fail(ctx, RSP_ERR_ARG, "bad dtype %d", dtype);
-    if (layout != RSP_ROWMAJOR && layout != RSP_COLMAJOR) return fail(ctx, RSP_ERR_ARG, "bad layout %d", layout);
-    if (P != ctx->p.P || R != ctx->p.R)
-        return fail(ctx, RSP_ERR_SHAPE, "echo is %lld x %lld but the context was created for %lld x %lld",
-                    (long long)P, (long long)R, (long long)ctx->p.P, (long long)ctx->p.R);
-    if (!set_device(ctx)) return fail(ctx, RSP_ERR_HIP, "hipSetDevice failed");
-    return RSP_OK;
-}
-
-// ---- pipelined host path
-static constexpr size_t kHostPiece = 8u << 20;        // pinned piece
-static constexpr size_t kHostChunkBytes = 32u << 20;  // device-side input bytes per host chunk
-                                                      // (c3: 8 CPIs; tools/host_probe.py)
-
-static int host_pipe_init(rsp_ctx* ctx) {
-    auto& h = ctx->hp;
-    if (h.s_h2d) return RSP_OK;
-    HIP_TRY(ctx, hipStreamCreateWithFlags(&h.s_h2d, hipStreamNonBlocking));
-    HIP_TRY(ctx, hipStreamCreateWithFlags(&h.s_d2h, hipStreamNonBlocking));
-    for (int i = 0; i < h.kSlots; ++i) {
-        HIP_TRY(ctx, hipEventCreateWithFlags(&h.ev_in[i], hipEventDisableTiming));
-        HIP_TRY(ctx, hipEventCreateWithFlags(&h.ev_comp[i], hipEventDisableTiming));
-        HIP_TRY(ctx, hipEventCreateWithFlags(&h.ev_out[i], hipEventDisableTiming));
-    }
-    for (auto& e : h.ev_part) HIP_TRY(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    h.piece = kHostPiece;
-    for (int i = 0; i < h.kRing; ++i) {
-        HIP_TRY(ctx, hipHostMalloc(&h.pin_in[i], h.piece, hipHostMallocDefault));
-        HIP_TRY(ctx, hipHostMalloc(&h.pin_out[i], h.piece, hipHostMallocDefault));
-        HIP_TRY(ctx, hipEventCreateWithFlags(&h.ev_pin_in[i], hipEventDisableTiming));
-        HIP_TRY(ctx, hipEventCreateWithFlags(&h.ev_pin_out[i], hipEventDisableTiming));
-    }
-    return RSP_OK;
-}
-
-// (thread creation can throw: callers run inside rsp_pc_mtd_cfar's try block, which turns any
-// exception into an error status -- nothing may unwind through the extern "C" boundary into
-// the MEX host)
-static rsp::CopyPool& host_pool(rsp_ctx* ctx) {
-    auto& h = ctx->hp;
-    int want = h.threads;
-    if (want <= 0) {
-        const unsigned hc = std::thread::hardware_concurrency();
-        want = hc >= 16 ? 8 : (hc >= 4 ? (int)hc / 2 : 1);
-    }
-    if (!h.pool || h.pool->threads() != want) {
-        h.pool.reset();
-        h.pool.reset(new rsp::CopyPool(want));
-    }
-    return *h.pool;
-}
-
-// host (pageable) -> device, through the pinned input ring on the H2D stream: piece i is
-// copied into a ring slot by the pool while the DMA of piece i-1 runs.
-// Piece size for a transfer of `bytes`: the ring's 8 MiB, but at least four pieces per transfer
-// down to 1 MiB, so a small call (one CPI: 8 MiB of C128 echo) still overlaps its memcpy with
-// its DMA.
-static size_t piece_for(const rsp_ctx* ctx, size_t bytes) {
-    size_t p = (bytes / 4 + 4095) & ~(size_t)4095;
-    if (p < ((size_t)1 << 20)) p = (size_t)1 << 20;
-    return p < ctx->hp.piece ? p : ctx->hp.piece;
-}
-
-// `bytes` = the device-side bytes; narrow: src is complex double, narrowed to complex float on
-// the way into the pinned piece (half the PCIe bytes of MATLAB's C128 echo).
-// narrow 2: src is real double, narrowed to float the same way (rsp_cfar_f64).
-static int h2d_pieces(rsp_ctx* ctx, void* d, const void* src, size_t bytes, int narrow = 0) {
-    auto& h = ctx->hp;
-    rsp::CopyPool& pool = host_pool(ctx);
-    const size_t piece = piece_for(ctx, bytes);
-    for (size_t off = 0; off < bytes; off += piece) {
-        const size_t n = bytes - off < piece ? bytes - off : piece;
-        const int r = h.ring_in;
-        h.ring_in = (h.ring_in + 1) % h.kRing;
-        HIP_TRY(ctx, hipEventSynchronize(h.ev_pin_in[r]));   // the slot's previous DMA is done
-        if (narrow == 2)
-            pool.narrow_f64((float*)h.pin_in[r], (const double*)((const char*)src + 2 * off), n / 4);
-        else if (narrow)
-            pool.narrow_c128((float*)h.pin_in[r], (const double*)((const char*)src + 2 * off), n / 8);
-        else
-            pool.copy(h.pin_in[r], (const char*)src + off, n);
-        HIP_TRY(ctx, hipMemcpyAsync((char*)d + off, h.pin_in[r], n, hipMemcpyHostToDevice, h.s_h2d));
-        HIP_TRY(ctx, hipEventRecord(h.ev_pin_in[r], h.s_h2d));
-    }
-    return RSP_OK;
-}
-
-// device -> host (pageable), through the pinned output ring on the D2H stream: up to kRing
-// pieces in flight; each is copied out by the pool once its DMA is done.
-// widen: the host side takes MATLAB's double -- 1: float cells, 2: 0/1 bytes -- converted by the
-// pool as each pinned piece lands (bytes = device-side bytes; the host array is 8 bytes per element)
-struct D2HPart {
-    const void* d;
-    void* h;
-    size_t bytes;
-    int widen = 0;
-};
-static int d2h_pieces(rsp_ctx* ctx, const std::vector<D2HPart>& parts) {
-    auto& h = ctx->hp;
-    rsp::CopyPool& pool = host_pool(ctx);
-    struct Piece {
-        const char* d;
-        char* h;
-        size_t n;
-        int widen;
-    };
-    std::vector<Piece> ps;
-    for (const D2HPart& p : parts) {
-        const size_t piece = piece_for(ctx, p.bytes);
-        const size_t scale = p.widen == 1 ? 2 : (p.widen == 2 ? 8 : 1);   // host bytes per device byte
-        for (size_t off = 0; off < p.bytes; off += piece)
-            ps.push_back({(const char*)p.d + off, (char*)p.h + off * scale, p.bytes - off < piece ? p.bytes - off : piece,
-                          p.widen});
-    }
-    const size_t np = ps.size();
-    auto issue = [&](size_t i) -> int {
-        const int r = (int)(i % h.kRing);
-        HIP_TRY(ctx, hipMemcpyAsync(h.pin_out[r], ps[i].d, ps[i].n, hipMemcpyDeviceToHost, h.s_d2h));
-        HIP_TRY(ctx, hipEventRecord(h.ev_pin_out[r], h.s_d2h));
-        return RSP_OK;
-    };
-    int rc;
-    for (size_t i = 0; i < np && i < (size_t)h.kRing; ++i)
-        if ((rc = issue(i))) return rc;
-    for (size_t i = 0; i < np; ++i) {
-        const int r = (int)(i % h.kRing);
-        HIP_TRY(ctx, hipEventSynchronize(h.ev_pin_out[r]));
-        if (h.pf) h.pf->wait(ps[i].h, ps[i].n * (ps[i].widen == 1 ? 2 : (ps[i].widen == 2 ? 8 : 1)));
-        if (ps[i].widen == 1) pool.widen_f32((double*)ps[i].h, (const float*)h.pin_out[r], ps[i].n / 4);
-        else if (ps[i].widen == 2) pool.widen_u8((double*)ps[i].h, (const uint8_t*)h.pin_out[r], ps[i].n);
-        else pool.copy(ps[i].h, h.pin_out[r], ps[i].n);
-        if (i + h.kRing < np && (rc = issue(i + h.kRing))) return rc;
-    }
-    return RSP_OK;
-}
-
-int rsp_set_host_pipeline(rsp_ctx* ctx, int64_t cpis_per_chunk, int32_t copy_threads) {
-    if (!ctx) return fail(nullptr, RSP_ERR_ARG, "null ctx");
-    if (cpis_per_chunk < 0 || copy_threads < 0 || copy_threads > 64)
-        return fail(ctx, RSP_ERR_ARG, "rsp_set_host_pipeline: chunk %lld, threads %d", (long long)cpis_per_chunk,
-                    (int)copy_threads);
-    ctx->host_chunk = cpis_per_chunk;
-    ctx->hp.threads = copy_threads;
-    return RSP_OK;
-}
-
-static int host_chain(rsp_ctx* ctx, const void* echo, int32_t dtype, int32_t layout, int64_t P, int64_t R,
-                      int64_t batch, const rsp_cfar_params* cfar, void* rdm_out, int32_t out_layout,
-                      void* flag_out, void* flagV_out, bool f64);
-
-// The host-buffer chain: float / byte outputs, or (f64) MATLAB's double outputs.
-static int host_call(rsp_ctx* ctx, const void* echo, int32_t dtype, int32_t layout, int64_t P, int64_t R,
-                     int64_t batch, const rsp_cfar_params* cfar, void* rdm_out, int32_t out_layout, void* flag_out,
-                     void* flagV_out, bool f64) {
-    if (!ctx) return fail(nullptr, RSP_ERR_ARG, "null ctx");
-    int rc;
-    try {
-        rc = host_chain(ctx, echo, dtype, layout, P, R, batch, cfar, rdm_out, out_layout, flag_out, flagV_out, f64);
-    } catch (const std::bad_alloc&) {
-        rc = fail(ctx, RSP_ERR_NOMEM, "rsp_pc_mtd_cfar: host allocation failed");
-    } catch (const std::exception& e) {
-        rc = fail(ctx, RSP_ERR_NOMEM, "rsp_pc_mtd_cfar: host pipeline: %s", e.what());
-    } catch (...) {
-        rc = fail(ctx, RSP_ERR_NOMEM, "rsp_pc_mtd_cfar: host pipeline: unknown exception");
-    }
-    if (rc && ctx->hp.s_h2d) {
-        // an error after chunks were issued: drain all three streams before returning, so the
-        // next call's first H2D cannot overwrite an input slot a chain still reads, nor its
-        // output staging race a D2H still in flight (the status stays the first error's)
-        (void)hipStreamSynchronize(ctx->hp.s_h2d);
-        (void)hipStreamSynchronize(ctx->stream);
-        (void)hipStreamSynchronize(ctx->hp.s_d2h);
-    }
-    return rc;
-}
-
-int rsp_pc_mtd_cfar(rsp_ctx* ctx, const void* echo, int32_t dtype, int32_t layout, int64_t P, int64_t R,
-                    int64_t batch, const rsp_cfar_params* cfar, float* rdm_out, int32_t out_layout,
-                    uint8_t* flag_out, uint8_t* flagV_out) {
-    return host_call(ctx, echo, dtype, layout, P, R, batch, cfar, rdm_out, out_layout, flag_out, flagV_out, false);
-}
-
-int rsp_pc_mtd_cfar_f64(rsp_ctx* ctx, const void* echo, int32_t dtype, int32_t layout, int64_t P, int64_t R,
-                        int64_t batch, const rsp_cfar_params* cfar, double* rdm_out, int32_t out_layout,
-                        double* flag_out, double* flagV_out) {
-    return host_call(ctx, echo, dtype, layout, P, R, batch, cfar, rdm_out, out_layout, flag_out, flagV_out, true);
-}
-
-// Dev-only host-path trace (environment RSP_HOST_TRACE=1): per call, host time of the setup, the
-// input staging (narrowing + DMA issue), the chain enqueue, the output staging (waits + widening)
-// and the final syncs, plus device time of the H2D / chain / D2H streams (timing events), on
-// stderr.  Used by tools/mex_bench.py --trace to find where a one-CPI MEX call spends its time.
-struct HostTrace {
-    bool on = false;
-    std::chrono::steady_clock::time_point t[8];
-    int n = 0;
-    hipEvent_t e[6] = {};
-    double acc[4] = {};   // one-chunk path: input conversion, output waits, output conversion (us)
-    void mark() { if (on && n < 8) t[n++] = std::chrono::steady_clock::now(); }
-    double now_us() const {
-        return on ? std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count() : 0.0;
-    }
-    void ev(int i, hipStream_t st) { if (on) (void)hipEventRecord(e[i], st); }
-};
-static bool host_trace_on() {
-    static const bool on = [] { const char* v = getenv("RSP_HOST_TRACE"); return v && *v == '1'; }();
-    return on;
-}
-
-// One-chunk calls (MATLAB's granularity: fun_MTD_produce is one CPI per call) are latency-bound,
-// not bandwidth-bound: a pinned DMA pays ~13 us of fixed cost per copy and ~11 us more to
-// signal the host (tools/micro/host_latency_probe.hip, profiles/r05/mex/), and the host's
-// narrowing / widening sat between DMAs on the critical path.  Here the kernels move the data
-// across PCIe themselves:
-//   * input: the copy threads narrow (or copy) the caller's echo into pinned staging in pieces
-//     of ~1 MiB that never cross a plane; right behind each piece, a transpose (column-major) or
-//     copy (row-major) kernel on the chain's stream reads it from pinned memory into the
-//     chain's device input -- PCIe transfer, ingest transpose and host narrowing overlap;
-//   * output: after the chain, transpose / copy kernels write the RDM and flag planes into
-//     pinned staging in up to kParts parts, an event behind each; the copy threads widen (or
-//     copy) part q into the caller's arrays while parts q+1.. cross the link.
-// Staging is allocated coherent (fine-grained: not cached in the GPU's L2), so a kernel never
-// reads a previous call's input from L2 and the host never reads output lines the L2 still holds.
-// RSP_HOST_ZC=0 (dev A/B) restores the DMA pipeline for every call.
-static constexpr size_t kZcPiece = 1u << 20;       // device bytes per input piece
-static constexpr size_t kZcMaxIn = 64u << 20;      // one-chunk calls up to this much device input
-static int zc_knob(const char* name, int dflt) {   // dev A/B knobs of the one-chunk path
-    const char* v = getenv(name);
-    return v && *v ? atoi(v) : dflt;
-}
-static int zc_mode() {
-    static const int m = [] { const char* v = getenv("RSP_HOST_ZC"); return v && *v ? atoi(v) : 1; }();
-    return m;
-}
-static int zc_ensure(rsp_ctx* ctx, void** p, size_t* n, size_t bytes) {
-    if (*p && *n >= bytes) return RSP_OK;
-    if (*p) {
-        HIP_TRY(ctx, hipHostFree(*p));
-        *p = nullptr;
-        *n = 0;
-    }
-    HIP_TRY(ctx, hipHostMalloc(p, bytes, zc_mode() == 2 ? hipHostMallocDefault : hipHostMallocCoherent));
-    *n = bytes;
-    return RSP_OK;
-}
-
-// Output delivery of the one-chunk paths: planes [batch][V][Ro] of each output (device, `es`
-// bytes per element: 4 float, 1 byte) are transposed (tr: the caller's column-major [Ro][V]) or
-// copied into pinned staging by kernels on ctx->stream, in parts of whole range-bin rows with an
-// event behind each; the copy threads deliver part q -- widened to double when f64 -- into the
-// caller's array while the later parts cross the link.
-struct ZcOut {
-    const void* dev;
-    int es;
-    void* host;
-    bool f64;
-};
-static int zc_deliver(rsp_ctx* ctx, const ZcOut* outs, int nout, int64_t batch, int64_t V, int64_t Ro, bool tr,
-                      HostTrace& ht) {
-    auto& h = ctx->hp;
-    const size_t cells = (size_t)V * Ro, ocells = (size_t)batch * cells;
-    size_t bytes = 0;
-    for (int k = 0; k < nout; ++k) bytes += ocells * outs[k].es;
-    int rc;
-    if ((rc = zc_ensure(ctx, &h.zc_out, &h.zc_out_n, bytes))) return rc;
-    hipStream_t st = ctx->stream;
-    struct Part {
-        int k;
-        size_t off, n;
-    };
-    Part parts[rsp_ctx::HostPipe::kParts];
-    int np = 0;
-    // parts of >= ~1 MiB of device output (a part costs a kernel and an event: at c3, 2 parts of
-    // the 2 MiB RDM beat 4 of 512 KiB; executeCFAR's ~170 KB segments go whole), within kParts
-    static const size_t kPartBytes = (size_t)zc_knob("RSP_ZC_PART_KIB", 1024) << 10;
-    const int budget = h.kParts / (nout * (int)batch);
-    char* zk[3] = {};
-    size_t zoff = 0;
-    for (int k = 0; k < nout; ++k) {
-        zk[k] = (char*)h.zc_out + zoff;
-        zoff += ocells * outs[k].es;
-    }
-    for (int k = 0; k < nout; ++k) {
-        const size_t es = (size_t)outs[k].es;
-        const int elem = es == 4 ? rsp::RSP_SUB_F32 : rsp::RSP_SUB_U8;
-        int per_plane = (int)((cells * es + kPartBytes / 2) / kPartBytes);
-        per_plane = per_plane < 1 ? 1 : (per_plane > budget ? budget : per_plane);
-        if (tr) {   // plane b: [V][Ro] -> [Ro][V]; a part = output rows [c0, c1) (range bins)
-            int64_t cp = (Ro + per_plane - 1) / per_plane;
-            cp = (cp + 31) / 32 * 32;
-            for (int64_t b = 0; b < batch; ++b)
-                for (int64_t c0 = 0; c0 < Ro; c0 += cp) {
-                    const int64_t c1 = c0 + cp < Ro ? c0 + cp : Ro;
-                    HIP_TRY(ctx, rsp::launch_transpose_sub(elem, (const char*)outs[k].dev + ((size_t)b * cells + c0) * es,
-                                                           zk[k] + (size_t)(b * Ro + c0) * V * es, (int)V, (int)(c1 - c0),
-                                                           (size_t)Ro, (size_t)V, st));
-                    HIP_TRY(ctx, hipEventRecord(h.ev_part[np], st));
-                    parts[np++] = {k, (size_t)(b * Ro + c0) * V, (size_t)(c1 - c0) * V};
-                }
-        } else {    // row-major: contiguous parts (whole 4-byte words: ocells % 4 == 0, checked)
-            const int nparts = per_plane * (int)batch;
-            size_t pe = (ocells + nparts - 1) / nparts;
-            pe = (pe + 1023) / 1024 * 1024;
-            for (size_t off = 0; off < ocells; off += pe) {
-                const size_t n = ocells - off < pe ? ocells - off : pe;
-                HIP_TRY(ctx, rsp::launch_copy_words((const char*)outs[k].dev + off * es, zk[k] + off * es, n * es / 4, st));
-                HIP_TRY(ctx, hipEventRecord(h.ev_part[np], st));
-                parts[np++] = {k, off, n};
-            }
-        }
-    }
-    ht.mark();   // 3: chain and output kernels enqueued
-    rsp::CopyPool& pool = host_pool(ctx);
-    for (int q = 0; q < np; ++q) {
-        const Part& pt = parts[q];
-        const ZcOut& o = outs[pt.k];
-        const double t0 = ht.now_us();
-        HIP_TRY(ctx, hipEventSynchronize(h.ev_part[q]));
-        const double t1 = ht.now_us();
-        const char* zp = zk[pt.k] + pt.off * o.es;
-        if (h.pf) h.pf->wait((char*)o.host + pt.off * (o.f64 ? 8 : o.es), pt.n * (o.f64 ? 8 : o.es));
-        if (o.es == 4) {
-            if (o.f64) pool.widen_f32((double*)o.host + pt.off, (const float*)zp, pt.n);
-            else pool.copy((float*)o.host + pt.off, zp, pt.n * 4);
-        } else {
-            if (o.f64) pool.widen_u8((double*)o.host + pt.off, (const uint8_t*)zp, pt.n);
-            else pool.copy((uint8_t*)o.host + pt.off, zp, pt.n);
-        }
-        ht.acc[1] += t1 - t0;
-        ht.acc[2] += ht.now_us() - t1;
-    }
-    return RSP_OK;
-}
-
-static int host_chain_small(rsp_ctx* ctx, const void* echo, int32_t dtype, int32_t layout, int64_t P, int64_t R,
-                            int64_t batch, const rsp_cfar_params* cfar, void* rdm_out, int32_t out_layout,
-                            void* flag_out, void* flagV_out, bool f64, HostTrace& ht, bool& taken) {
-    auto& h = ctx->hp;
-    taken = false;
-    const int64_t Ro = ctx->p.R_out, V = ctx->V, beams = ctx->beams;
-    const bool narrow = dtype == RSP_C128;
-    const int32_t ddtype = narrow ? RSP_C64 : dtype;
-    const size_t ein = dtype_size(dtype), edev = dtype_size(ddtype);
-    const bool conv = layout != RSP_ROWMAJOR, tr = out_layout == RSP_COLMAJOR;
-    const bool want_fv = cfar && flagV_out;
-    const int64_t planes = batch * beams;
-    const size_t elems = (size_t)planes * P * R, dbytes = elems * edev;
-    const size_t cells = (size_t)V * Ro, ocells = (size_t)batch * cells;
-    const int nkinds = (rdm_out ? 1 : 0) + (cfar ? 1 : 0) + (want_fv ? 1 : 0);
-    if (dbytes > kZcMaxIn || (int64_t)nkinds * batch > h.kParts || (!tr && (ocells % 4) != 0) ||
-        (!conv && (dbytes % 4) != 0))
-        return RSP_OK;   // not taken: the DMA pipeline runs the call
-    taken = true;
-    int rc;
-    if ((rc = zc_ensure(ctx, &h.zc_in, &h.zc_in_n, dbytes))) return rc;
-    if ((rc = ensure(ctx, h.in[0], dbytes))) return rc;
-    if (conv && (rc = ensure(ctx, h.canon[0], elems * sizeof(float2)))) return rc;
-    if ((rc = ensure(ctx, h.rdm[0], ocells * sizeof(float)))) return rc;
-    if (cfar && (rc = ensure(ctx, h.flag[0], ocells))) return rc;
-    if (want_fv && (rc = ensure(ctx, h.flagV[0], ocells))) return rc;
-    rsp::CopyPool& pool = host_pool(ctx);
-    hipStream_t st = ctx->stream;
-    char* zin = (char*)h.zc_in;
-    const char* src = (const char*)echo;
-    // ---- input pieces: source elements [s0, s0 + n)
-    auto stage = [&](size_t s0, size_t n) {
-        const double t0 = ht.now_us();
-        if (narrow) pool.narrow_c128((float*)(zin + s0 * edev), (const double*)(src + s0 * ein), n);
-        else pool.copy(zin + s0 * edev, src + s0 * ein, n * edev);
-        std::atomic_thread_fence(std::memory_order_release);
-        ht.acc[0] += ht.now_us() - t0;
-    };
-    static const size_t kPiece = (size_t)zc_knob("RSP_ZC_PIECE_KIB", (int)(kZcPiece >> 10)) << 10;
-    if (conv) {   // plane k = [R][P] -> canon [P][R]; a piece = rows [r0, r1) of one plane
-        int64_t rp = (int64_t)(kPiece / ((size_t)P * edev)) / 32 * 32;
-        if (rp < 32) rp = 32;
-        const int elem = ddtype == RSP_C32F16 ? rsp::RSP_SUB_C32F16 : rsp::RSP_SUB_C64;
-        for (int64_t k = 0; k < planes; ++k)
-            for (int64_t r0 = 0; r0 < R; r0 += rp) {
-                const int64_t r1 = r0 + rp < R ? r0 + rp : R;
-                const size_t s0 = (size_t)(k * R + r0) * P;
-                stage(s0, (size_t)(r1 - r0) * P);
-                HIP_TRY(ctx, rsp::launch_transpose_sub(elem, zin + s0 * edev,
-                                                       (float2*)h.canon[0].p + (size_t)k * P * R + r0, (int)(r1 - r0),
-                                                       (int)P, (size_t)P, (size_t)R, st));
-            }
-    } else {      // row-major: contiguous pieces, copied as they are
-        const size_t pe = (kPiece / edev + 1023) / 1024 * 1024;
-        for (size_t s0 = 0; s0 < elems; s0 += pe) {
-            const size_t n = elems - s0 < pe ? elems - s0 : pe;
-            stage(s0, n);
-            HIP_TRY(ctx, rsp::launch_copy_words(zin + s0 * edev, (char*)h.in[0].p + s0 * edev, n * edev / 4, st));
-        }
-    }
-    ht.mark();   // 2: input staged
-    ht.ev(2, st);
-    int rc2 = rsp_pc_mtd_cfar_dev(ctx, conv ? h.canon[0].p : h.in[0].p, conv ? RSP_C64 : ddtype, batch, cfar,
-                                  (float*)h.rdm[0].p, cfar ? (uint8_t*)h.flag[0].p : nullptr,
-                                  want_fv ? (uint8_t*)h.flagV[0].p : nullptr, st);
-    if (rc2) return rc2;
-    ht.ev(3, st);
-    ht.ev(4, st);
-    ZcOut outs[3];
-    int no = 0;
-    if (rdm_out) outs[no++] = {h.rdm[0].p, 4, rdm_out, f64};
-    if (cfar) outs[no++] = {h.flag[0].p, 1, flag_out, f64};
-    if (want_fv) outs[no++] = {h.flagV[0].p, 1, flagV_out, f64};
-    if ((rc = zc_deliver(ctx, outs, no, batch, V, Ro, tr, ht))) return rc;
-    ht.ev(5, st);
-    ht.mark();   // 4: outputs delivered
-    return RSP_OK;
-}
-
-// Prefault of the caller's output arrays (rsp_hostpool.h Prefaulter) from the start of a call
-// whose outputs total >= kPrefaultMin bytes: new arrays of that size are fresh anonymous
-// mappings (glibc serves allocations above its mmap threshold, at most 32 MiB, by mmap), and
-// the copy threads would otherwise take one page fault + zeroing per 4 KiB as they deliver.
-// The job ends (workers off the caller's memory) before the call returns, on every path.
-// Dev A/B: RSP_PREFAULT=0 off; RSP_PREFAULT_THREADS (default 4); RSP_PREFAULT_HUGE=0 (no
-// MADV_HUGEPAGE advice).  (Faulting on the calling thread's NUMA node was measured neutral on the
-// GPU box -- every page landed on node 0 either way, profiles/r06/host/numa_ab/ -- and is not
-// kept.)
-static constexpr size_t kPrefaultMin = 8u << 20;
-struct PrefaultJob {
-    rsp_ctx* ctx = nullptr;
-    ~PrefaultJob() {
-        if (ctx && ctx->hp.pf) {
-            ctx->hp.pf->end();
-            ctx->hp.pf = nullptr;
-        }
-    }
-};
-static void host_prefault(rsp_ctx* ctx, PrefaultJob& job, const std::vector<std::pair<void*, size_t>>& ranges) {
-    static const int mode = zc_knob("RSP_PREFAULT", 1);
-    static const int nthr = zc_knob("RSP_PREFAULT_THREADS", 4);
-    static const int huge = zc_knob("RSP_PREFAULT_HUGE", 1);
-    size_t total = 0;
-    for (const auto& r : ranges) total += r.first ? r.second : 0;
-    if (mode == 0 || total < kPrefaultMin) return;
-    auto& h = ctx->hp;
-    if (!h.prefault) h.prefault.reset(new rsp::Prefaulter(nthr, huge != 0));
-    std::vector<std::pair<void*, size_t>> rs;
-    for (const auto& r : ranges)
-        if (r.first && r.second) rs.push_back(r);
-    h.prefault->begin(rs);
-    h.pf = h.prefault.get();
-    job.ctx = ctx;
-}
-
-static int host_chain(rsp_ctx* ctx, const void* echo, int32_t dtype, int32_t layout, int64_t P, int64_t R,
-                      int64_t batch, const rsp_cfar_params* cfar, void* rdm_out, int32_t out_layout,
-                      void* flag_out, void* flagV_out, bool f64) {
-    HostTrace ht;
-    ht.on = host_trace_on();
-    if (ht.on)
-        for (auto& e : ht.e) (void)hipEventCreate(&e);
-    ht.mark();
-    int rc = check_host_call(ctx, echo, dtype, layout, P, R, batch);
-    if (rc) return rc;
-    if (out_layout != RSP_ROWMAJOR && out_layout != RSP_COLMAJOR) return fail(ctx, RSP_ERR_ARG, "bad out_layout");
-    if (cfar && !flag_out) return fail(ctx, RSP_ERR_ARG, "CFAR requested without flag_out");
-    if (!cfar && !rdm_out) return fail(ctx, RSP_ERR_ARG, "no output requested");
-    if (batch == 0) return RSP_OK;
-    if ((rc = host_pipe_init(ctx))) return rc;
-    auto& h = ctx->hp;
-    const int64_t Ro = ctx->p.R_out, V = ctx->V, beams = ctx->beams;
-    // MATLAB's complex double is narrowed to complex float by the host copy threads (the same
-    // round-to-nearest cast the device conversion does): half the PCIe bytes
-    const bool narrow = dtype == RSP_C128;
-    const int32_t ddtype = narrow ? RSP_C64 : dtype;              // what lands on the device
-    const size_t in_cpi = (size_t)beams * P * R * dtype_size(dtype);         // caller's bytes
-    const size_t dev_cpi = (size_t)beams * P * R * dtype_size(ddtype);       // device bytes
-    const size_t cells = (size_t)V * Ro;   // per CPI
-    const bool conv = layout != RSP_ROWMAJOR;   // column-major: transposed on the device
-    const bool tr = out_layout == RSP_COLMAJOR;
-    const bool want_fv = cfar && flagV_out;
-    int64_t K = ctx->host_chunk > 0 ? ctx->host_chunk : (int64_t)(kHostChunkBytes / dev_cpi);
-    if (K < 1) K = 1;
-    if (K > batch) K = batch;
-    const int64_t nk = (batch + K - 1) / K;
-    PrefaultJob pfjob;   // (ends the prefault job on every return below)
-    {
-        const size_t oc = (size_t)batch * cells, rb = f64 ? 8 : 4, fb = f64 ? 8 : 1;
-        host_prefault(ctx, pfjob, {{rdm_out, rdm_out ? oc * rb : 0}, {flag_out, cfar ? oc * fb : 0},
-                                   {flagV_out, want_fv ? oc * fb : 0}});
-    }
-    if (nk == 1 && zc_mode() != 0) {
-        ht.mark();   // 1: set up
-        bool taken = false;
-        rc = host_chain_small(ctx, echo, dtype, layout, P, R, batch, cfar, rdm_out, out_layout, flag_out, flagV_out,
-                              f64, ht, taken);
-        if (taken) {
-            if (rc == RSP_OK && ht.on) {
-                ht.mark();   // 5
-                (void)hipStreamSynchronize(ctx->stream);
-                float g[2] = {};
-                (void)hipEventElapsedTime(&g[0], ht.e[2], ht.e[3]);
-                (void)hipEventElapsedTime(&g[1], ht.e[4], ht.e[5]);
-                auto us = [&](int a, int b) { return std::chrono::duration<double, std::micro>(ht.t[b] - ht.t[a]).count(); };
-                fprintf(stderr, "rsp_host_trace batch %lld chunks 1 zc host_us setup %.1f stage_in %.1f enqueue %.1f "
-                        "stage_out %.1f sync %.1f total %.1f dev_us h2d 0 chain %.1f d2h %.1f zc_us narrow %.1f "
-                        "wait %.1f widen %.1f\n", (long long)batch,
-                        us(0, 1), us(1, 2), us(2, 3), us(3, 4), us(4, 5), us(0, 5), g[0] * 1e3, g[1] * 1e3, ht.acc[0],
-                        ht.acc[1], ht.acc[2]);
-            }
-            if (ht.on)
-                for (auto& e : ht.e) (void)hipEventDestroy(e);
-            return rc;
-        }
-        ht.n = 1;   // (the DMA pipeline's marks follow)
-    }
-    for (int i = 0; i < h.kSlots && i < nk; ++i) {
-        if ((rc = ensure(ctx, h.in[i], (size_t)K * dev_cpi))) return rc;
-        if (conv && (rc = ensure(ctx, h.canon[i], (size_t)K * beams * P * R * sizeof(float2)))) return rc;
-        if ((rc = ensure(ctx, h.rdm[i], (size_t)K * cells * sizeof(float)))) return rc;
-        if (cfar && (rc = ensure(ctx, h.flag[i], (size_t)K * cells))) return rc;
-        if (want_fv && (rc = ensure(ctx, h.flagV[i], (size_t)K * cells))) return rc;
-        if (tr) {
-            if (rdm_out && (rc = ensure(ctx, h.tr[i][0], (size_t)K * cells * sizeof(float)))) return rc;
-            if (cfar && (rc = ensure(ctx, h.tr[i][1], (size_t)K * cells))) return rc;
-            if (want_fv && (rc = ensure(ctx, h.tr[i][2], (size_t)K * cells))) return rc;
-        }
-    }
-    // chunk k: the chain on slot k % 2 after its H2D, then transposes; its outputs' D2H waits for it
-    auto chunk_n = [&](int64_t k) { return k == nk - 1 ? batch - k * K : K; };
-    auto compute = [&](int64_t k) -> int {
-        const int sl = (int)(k % h.kSlots);
-        const int64_t n = chunk_n(k);
-        HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, h.ev_in[sl], 0));
-        if (k >= h.kSlots) HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, h.ev_out[sl], 0));   // slot's D2H done
-        const void* d_echo = h.in[sl].p;
-        int32_t d_dtype = ddtype;
-        if (conv) {
-            HIP_TRY(ctx, rsp::launch_ingest(h.in[sl].p, ddtype, layout, (float2*)h.canon[sl].p, n * beams, (int)P,
-                                            (int)R, ctx->stream));
-            d_echo = h.canon[sl].p;
-            d_dtype = RSP_C64;
-        }
-        int rc2 = rsp_pc_mtd_cfar_dev(ctx, d_echo, d_dtype, n, cfar, (float*)h.rdm[sl].p,
-                                      cfar ? (uint8_t*)h.flag[sl].p : nullptr,
-                                      want_fv ? (uint8_t*)h.flagV[sl].p : nullptr, ctx->stream);
-        if (rc2) return rc2;
-        if (tr) {
-            if (rdm_out)
-                HIP_TRY(ctx, rsp::launch_transpose_f32((const float*)h.rdm[sl].p, (float*)h.tr[sl][0].p, n, (int)V,
-                                                       (int)Ro, ctx->stream));
-            if (cfar)
-                HIP_TRY(ctx, rsp::launch_transpose_u8((const uint8_t*)h.flag[sl].p, (uint8_t*)h.tr[sl][1].p, n, (int)V,
-                                                      (int)Ro, ctx->stream));
-            if (want_fv)
-                HIP_TRY(ctx, rsp::launch_transpose_u8((const uint8_t*)h.flagV[sl].p, (uint8_t*)h.tr[sl][2].p, n,
-                                                      (int)V, (int)Ro, ctx->stream));
-        }
-        HIP_TRY(ctx, hipEventRecord(h.ev_comp[sl], ctx->stream));
-        return RSP_OK;
-    };
-    auto output = [&](int64_t k) -> int {
-        const int sl = (int)(k % h.kSlots);
-        const size_t n = (size_t)chunk_n(k), o = (size_t)k * K * cells;
-        HIP_TRY(ctx, hipStreamWaitEvent(h.s_d2h, h.ev_comp[sl], 0));
-        std::vector<D2HPart> parts;
-        const size_t rb = f64 ? 8 : 4, fb = f64 ? 8 : 1;   // host bytes per RDM / flag element
-        if (rdm_out)
-            parts.push_back({tr ? h.tr[sl][0].p : h.rdm[sl].p, (char*)rdm_out + o * rb, n * cells * sizeof(float), f64 ? 1 : 0});
-        if (cfar) parts.push_back({tr ? h.tr[sl][1].p : h.flag[sl].p, (char*)flag_out + o * fb, n * cells, f64 ? 2 : 0});
-        if (want_fv)
-            parts.push_back({tr ? h.tr[sl][2].p : h.flagV[sl].p, (char*)flagV_out + o * fb, n * cells, f64 ? 2 : 0});
-        int rc2 = d2h_pieces(ctx, parts);
-        if (rc2) return rc2;
-        HIP_TRY(ctx, hipEventRecord(h.ev_out[sl], h.s_d2h));
-        return RSP_OK;
-    };
-    ht.mark();   // 1: set up
-    for (int64_t k = 0; k < nk; ++k) {
-        const int sl = (int)(k % h.kSlots);
-        // the slot's previous chain (chunk k-2) has read its input
-        if (k >= h.kSlots) HIP_TRY(ctx, hipStreamWaitEvent(h.s_h2d, h.ev_comp[sl], 0));
-        if (k == 0) ht.ev(0, h.s_h2d);
-        if ((rc = h2d_pieces(ctx, h.in[sl].p, (const char*)echo + (size_t)k * K * in_cpi, (size_t)chunk_n(k) * dev_cpi,
-                             narrow ? 1 : 0)))
-            return rc;
-        if (k == nk - 1) ht.ev(1, h.s_h2d);
-        HIP_TRY(ctx, hipEventRecord(h.ev_in[sl], h.s_h2d));
-        if (k == 0) ht.mark();   // 2: first chunk staged
-        if (k == 0) {
-            HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, h.ev_in[sl], 0));
-            ht.ev(2, ctx->stream);
-        }
-        if ((rc = compute(k))) return rc;
-        if (k == nk - 1) ht.ev(3, ctx->stream);
-        if (k == 0) ht.mark();   // 3: first chain enqueued
-        if (k >= 1 && (rc = output(k - 1))) return rc;
-    }
-    if (ht.on) {
-        HIP_TRY(ctx, hipStreamWaitEvent(h.s_d2h, h.ev_comp[(nk - 1) % h.kSlots], 0));
-        ht.ev(4, h.s_d2h);
-    }
-    if ((rc = output(nk - 1))) return rc;
-    ht.ev(5, h.s_d2h);
-    ht.mark();   // 4: outputs staged
-    HIP_TRY(ctx, hipStreamSynchronize(h.s_d2h));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    ht.mark();   // 5: done
-    if (ht.on) {
-        float g[3] = {};
-        (void)hipEventElapsedTime(&g[0], ht.e[0], ht.e[1]);
-        (void)hipEventElapsedTime(&g[1], ht.e[2], ht.e[3]);
-        (void)hipEventElapsedTime(&g[2], ht.e[4], ht.e[5]);
-        auto us = [&](int a, int b) { return std::chrono::duration<double, std::micro>(ht.t[b] - ht.t[a]).count(); };
-        fprintf(stderr, "rsp_host_trace batch %lld chunks %lld host_us setup %.1f stage_in %.1f enqueue %.1f stage_out %.1f "
-                "sync %.1f total %.1f dev_us h2d %.1f chain %.1f d2h %.1f\n", (long long)batch, (long long)nk, us(0, 1),
-                us(1, 2), us(2, 3), us(3, 4), us(4, 5), us(0, 5), g[0] * 1e3, g[1] * 1e3, g[2] * 1e3);
-        for (auto& e : ht.e) (void)hipEventDestroy(e);
-    }
-    return RSP_OK;
-}
-
-int rsp_pc_mtd(rsp_ctx* ctx, const void* echo, int32_t dtype, int32_t layout, int64_t P, int64_t R,
-               int64_t batch, float* rdm_out, int32_t rdm_layout) {
-    if (!rdm_out) return fail(ctx, RSP_ERR_ARG, "rsp_pc_mtd: null rdm_out");
-    return rsp_pc_mtd_cfar(ctx, echo, dtype, layout, P, R, batch, nullptr, rdm_out, rdm_layout, nullptr, nullptr);
-}
-
-int rsp_cfar(rsp_ctx* ctx, const float* rdm, int32_t rdm_layout, int64_t V, int64_t R, int64_t batch,
-             const rsp_cfar_params* cfar, uint8_t* flag_out, uint8_t* flagV_out) {
-    if (!ctx) return fail(nullptr, RSP_ERR_ARG, "null ctx");
-    if (!rdm || !cfar || !flag_out || V < 1 || R < 1 || batch < 0) return fail(ctx, RSP_ERR_ARG, "rsp_cfar: bad argument");
-    if (rdm_layout != RSP_ROWMAJOR && rdm_layout != RSP_COLMAJOR) return fail(ctx, RSP_ERR_ARG, "bad rdm_layout");
-    if (batch == 0) return RSP_OK;
-    if (!set_device(ctx)) return fail(ctx, RSP_ERR_HIP, "hipSetDevice failed");
-    const size_t cells = (size_t)batch * V * R;
-    int rc;
-    if ((rc = ensure(ctx, ctx->st_in, cells * sizeof(float)))) return rc;
-    if ((rc = ensure(ctx, ctx->st_rdm, cells * sizeof(float)))) return rc;
-    if ((rc = ensure(ctx, ctx->st_flag, cells))) return rc;
-    if ((rc = ensure(ctx, ctx->st_flagV, cells))) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->st_in.p, rdm, cells * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-    const float* d_rdm = (const float*)ctx->st_in.p;
-    if (rdm_layout == RSP_COLMAJOR) {  // MATLAB V x R = [b][R][V] -> [b][V][R]
-        HIP_TRY(ctx, rsp::launch_transpose_f32(d_rdm, (float*)ctx->st_rdm.p, batch, (int)R, (int)V, ctx->stream));
-        d_rdm = (const float*)ctx->st_rdm.p;
-    }
-    rc = rsp_cfar_dev(ctx, d_rdm, V, R, batch, cfar, (uint8_t*)ctx->st_flag.p, (uint8_t*)ctx->st_flagV.p, ctx->stream);
-    if (rc) return rc;
-    if ((rc = fetch(ctx, (const uint8_t*)ctx->st_flag.p, flag_out, batch, V, R, rdm_layout))) return rc;
-    if (flagV_out && (rc = fetch(ctx, (const uint8_t*)ctx->st_flagV.p, flagV_out, batch, V, R, rdm_layout)))
-        return rc;
-    return RSP_OK;
-}
-
-// executeCFAR with MATLAB's types (rsp.h): the double RDM narrowed to float by the copy pool on
-// its way into the pinned input ring, the 0/1 flags widened to double as their pieces land.
-static int cfar_f64_body(rsp_ctx* ctx, const double* rdm, int32_t rdm_layout, int64_t V, int64_t R, int64_t batch,
-                         const rsp_cfar_params* cfar, double* flag_out, double* flagV_out) {
-    int rc;
-    if ((rc = host_pipe_init(ctx))) return rc;
-    const size_t cells = (size_t)batch * V * R;
-    if ((rc = ensure(ctx, ctx->st_in, cells * sizeof(float)))) return rc;
-    if ((rc = ensure(ctx, ctx->st_rdm, cells * sizeof(float)))) return rc;
-    if ((rc = ensure(ctx, ctx->st_flag, cells))) return rc;
-    if ((rc = ensure(ctx, ctx->st_flagV, cells))) return rc;
-    auto& h = ctx->hp;
-    const bool col = rdm_layout == RSP_COLMAJOR;
-    if (zc_mode() != 0 && cells * sizeof(float) <= kZcMaxIn && (flagV_out ? 2 : 1) * batch <= h.kParts &&
-        (col || cells % 4 == 0)) {
-        // one chunk (executeCFAR's segments): the narrowed pieces are read from pinned staging by
-        // the transpose / copy kernels, the flags written back into it part by part (host_chain_small)
-        if ((rc = zc_ensure(ctx, &h.zc_in, &h.zc_in_n, cells * sizeof(float)))) return rc;
-        rsp::CopyPool& pool = host_pool(ctx);
-        char* zin = (char*)h.zc_in;
-        hipStream_t st = ctx->stream;
-        if (col) {   // plane k = [R][V] -> [V][R]; a piece = rows [r0, r1) of one plane
-            int64_t rp = (int64_t)(kZcPiece / ((size_t)V * sizeof(float))) / 32 * 32;
-            if (rp < 32) rp = 32;
-            for (int64_t k = 0; k < batch; ++k)
-                for (int64_t r0 = 0; r0 < R; r0 += rp) {
-                    const int64_t r1 = r0 + rp < R ? r0 + rp : R;
-                    const size_t s0 = (size_t)(k * R + r0) * V;
-                    pool.narrow_f64((float*)zin + s0, rdm + s0, (size_t)(r1 - r0) * V);
-                    std::atomic_thread_fence(std::memory_order_release);
-                    HIP_TRY(ctx, rsp::launch_transpose_sub(rsp::RSP_SUB_F32, (float*)zin + s0,
-                                                           (float*)ctx->st_rdm.p + (size_t)k * V * R + r0, (int)(r1 - r0),
-                                                           (int)V, (size_t)V, (size_t)R, st));
-                }
-        } else {
-            const size_t pe = kZcPiece / sizeof(float);
-            for (size_t s0 = 0; s0 < cells; s0 += pe) {
-                const size_t n = cells - s0 < pe ? cells - s0 : pe;
-                pool.narrow_f64((float*)zin + s0, rdm + s0, n);
-                std::atomic_thread_fence(std::memory_order_release);
-                HIP_TRY(ctx, rsp::launch_copy_words((float*)zin + s0, (float*)ctx->st_in.p + s0, n, st));
-            }
-        }
-        rc = rsp_cfar_dev(ctx, (const float*)(col ? ctx->st_rdm.p : ctx->st_in.p), V, R, batch, cfar,
-                          (uint8_t*)ctx->st_flag.p, (uint8_t*)ctx->st_flagV.p, st);
-        if (rc) return rc;
-        ZcOut outs[2] = {{ctx->st_flag.p, 1, flag_out, true}, {ctx->st_flagV.p, 1, flagV_out, true}};
-        HostTrace none;
-        return zc_deliver(ctx, outs, flagV_out ? 2 : 1, batch, V, R, col, none);
-    }
-    if ((rc = h2d_pieces(ctx, ctx->st_in.p, rdm, cells * sizeof(float), 2))) return rc;
-    HIP_TRY(ctx, hipEventRecord(h.ev_in[0], h.s_h2d));
-    HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, h.ev_in[0], 0));
-    const float* d_rdm = (const float*)ctx->st_in.p;
-    if (col) {  // MATLAB V x R = [b][R][V] -> [b][V][R]
-        HIP_TRY(ctx, rsp::launch_transpose_f32(d_rdm, (float*)ctx->st_rdm.p, batch, (int)R, (int)V, ctx->stream));
-        d_rdm = (const float*)ctx->st_rdm.p;
-    }
-    rc = rsp_cfar_dev(ctx, d_rdm, V, R, batch, cfar, (uint8_t*)ctx->st_flag.p, (uint8_t*)ctx->st_flagV.p, ctx->stream);
-    if (rc) return rc;
-    const uint8_t* f = (const uint8_t*)ctx->st_flag.p;
-    const uint8_t* fv = (const uint8_t*)ctx->st_flagV.p;
-    if (col) {   // back to MATLAB's [b][R][V]
-        if ((rc = ensure(ctx, ctx->st_t, cells))) return rc;
-        if ((rc = ensure(ctx, ctx->st_canon, cells))) return rc;
-        HIP_TRY(ctx, rsp::launch_transpose_u8(f, (uint8_t*)ctx->st_t.p, batch, (int)V, (int)R, ctx->stream));
-        f = (const uint8_t*)ctx->st_t.p;
-        if (flagV_out) {
-            HIP_TRY(ctx, rsp::launch_transpose_u8(fv, (uint8_t*)ctx->st_canon.p, batch, (int)V, (int)R, ctx->stream));
-            fv = (const uint8_t*)ctx->st_canon.p;
-        }
-    }
-    HIP_TRY(ctx, hipEventRecord(h.ev_comp[0], ctx->stream));
-    HIP_TRY(ctx, hipStreamWaitEvent(h.s_d2h, h.ev_comp[0], 0));
-    std::vector<D2HPart> parts;
-    parts.push_back({f, flag_out, cells, 2});
-    if (flagV_out) parts.push_back({fv, flagV_out, cells, 2});
-    if ((rc = d2h_pieces(ctx, parts))) return rc;
-    HIP_TRY(ctx, hipStreamSynchronize(h.s_d2h));
-    return RSP_OK;
-}
-
-int rsp_cfar_f64(rsp_ctx* ctx, const double* rdm, int32_t rdm_layout, int64_t V, int64_t R, int64_t batch,
-                 const rsp_cfar_params* cfar, double* flag_out, double* flagV_out) {
-    if (!ctx) return fail(nullptr, RSP_ERR_ARG, "null ctx");
-    if (!rdm || !cfar || !flag_out || V < 1 || R < 1 || batch < 0) return fail(ctx, RSP_ERR_ARG, "rsp_cfar_f64: bad argument");
-    if (rdm_layout != RSP_ROWMAJOR && rdm_layout != RSP_COLMAJOR) return fail(ctx, RSP_ERR_ARG, "bad rdm_layout");
-    if (batch == 0) return RSP_OK;
-    if (!set_device(ctx)) return fail(ctx, RSP_ERR_HIP, "hipSetDevice failed");
-    int rc;
-    try {
-        rc = cfar_f64_body(ctx, rdm, rdm_layout, V, R, batch, cfar, flag_out, flagV_out);
-    } catch (const std::exception& e) {
-        rc = fail(ctx, RSP_ERR_NOMEM, "rsp_cfar_f64: host pipeline: %s", e.what());
-    } catch (...) {
-        rc = fail(ctx, RSP_ERR_NOMEM, "rsp_cfar_f64: host pipeline: unknown exception");
-    }
-    if (rc && ctx->hp.s_h2d) {
-        (void)hipStreamSynchronize(ctx->hp.s_h2d);
-        (void)hipStreamSynchronize(ctx->stream);
-        (void)hipStreamSynchronize(ctx->hp.s_d2h);
-    }
-    return rc;
-}
-

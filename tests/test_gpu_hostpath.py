@@ -252,8 +252,8 @@ def test_one_chunk_two_beam(torch_cuda):
 def test_cfar_f64_dma_fallback_matches_cfar(torch_cuda):
     """rsp_cfar_f64 beyond the one-chunk limit (more than kParts = 16 output parts: batch 20 with
     flagV) takes the DMA pipeline instead of pinned staging: the double RDM narrowed by the copy
-    threads on its way into the pinned input ring (h2d_pieces narrow 2), the u8 flag transposes for
-    MATLAB's layout, and the flags widened to double as their pieces land (d2h widen 2).  Both
+    threads on its way into the pinned input ring (h2d_pieces, f64 -> f32), the u8 flag transposes for
+    MATLAB's layout, and the flags widened to double as their pieces land (d2h_pieces, u8 -> f64).  Both
     layouts, bit-exact against rsp_cfar on the same (float-representable) values."""
     import ctypes as C
     from rsp import _capi as capi
@@ -278,6 +278,45 @@ def test_cfar_f64_dma_fallback_matches_cfar(torch_cuda):
         assert lib.rsp_cfar_f64(eng.ctx, ptr(x64), lay, V, R, B, C.byref(cp), ptr(f64), ptr(v64)) == 0
         assert np.array_equal(f64, f8.astype(np.float64)) and np.array_equal(v64, v8.astype(np.float64))
         assert v8.sum() > 0
+    eng.close()
+
+
+def test_cfar_f64_ragged_pieces_and_parts_match_cfar(torch_cuda):
+    """rsp_cfar_f64's one-chunk path where neither the input pieces nor the output parts divide
+    evenly: V=512, R=4000, batch 2 on a CFAR-only context.  Column-major, a plane goes in as
+    pieces of 512 range rows with a last one of 416, and each flag plane comes back as range
+    bins [0, 2016) and [2016, 4000); row-major, the last contiguous piece and part are short.
+    Hits sit in the last input piece and on both sides of bin 2016.  Both layouts, with and
+    without flagV_out, bit-exact against rsp_cfar on the same (float-representable) values;
+    the outputs start as 7.0, so a cell that is never delivered fails the comparison."""
+    import ctypes as C
+    from rsp import _capi as capi
+    from rsp import presets
+    from rsp.engine import Engine
+    eng = Engine(None)
+    cp = presets.Cfar().to_c()
+    lib = eng.lib
+    V, R, B = 512, 4000, 2
+    rng = np.random.default_rng(416)
+    rdm = np.abs(rng.standard_normal((B, V, R)) + 1j * rng.standard_normal((B, V, R))).astype(np.float32)
+    hits = [(100, 3700), (300, 2010), (301, 2020), (150, 40), (400, 1024)]
+    for v, r in hits:
+        rdm[:, v, r] = 60.0
+    ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None   # noqa: E731
+    for lay in (capi.RSP_ROWMAJOR, capi.RSP_COLMAJOR):
+        x = rdm if lay == capi.RSP_ROWMAJOR else np.ascontiguousarray(np.swapaxes(rdm, 1, 2))
+        f8, v8 = np.empty(x.shape, np.uint8), np.empty(x.shape, np.uint8)
+        assert lib.rsp_cfar(eng.ctx, ptr(x), lay, V, R, B, C.byref(cp), ptr(f8), ptr(v8)) == 0
+        rows = f8 if lay == capi.RSP_ROWMAJOR else np.swapaxes(f8, 1, 2)
+        for v, r in hits[:3]:
+            assert rows[:, v, r].all()
+        x64 = x.astype(np.float64)
+        for want_fv in (True, False):
+            f64, v64 = np.full(x.shape, 7.0), (np.full(x.shape, 7.0) if want_fv else None)
+            assert lib.rsp_cfar_f64(eng.ctx, ptr(x64), lay, V, R, B, C.byref(cp), ptr(f64), ptr(v64)) == 0
+            assert np.array_equal(f64, f8.astype(np.float64))
+            assert v64 is None or np.array_equal(v64, v8.astype(np.float64))
+            assert f64.sum() > 0
     eng.close()
 
 

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Median phase times of the host-path trace lines (RSP_HOST_TRACE=1, rsp_capi.cpp HostTrace)
+"""Median phase times of the host-path trace lines (RSP_HOST_TRACE=1, rsp_host.cpp HostTrace)
 in a stderr capture:  python tools/parse_host_trace.py gpurun_out/mex_trace.err"""
 import statistics as st
 import sys
