@@ -464,6 +464,56 @@ int rsp_ingest_frame_dev(rsp_ctx* ctx, const uint8_t* d_stream, int64_t nbytes, 
                          const float* d_dbf, void* d_out, int64_t beam_stride, uint16_t* d_servo,
                          int32_t* d_status, void* stream);
 
+/* ---- legacy two-beam 24-bit records (frameDataRead_A) ------------------------------------ */
+/* nframes x prt_num consecutive PRT records of the legacy capture format -> the left and right
+ * beams' echo planes, replacing the per-PRT loop of
+ *   [echoData_Frame_Left, echoData_Frame_Right, frameInd, modFlag, beamPosNum, beamNums, freInd,
+ *    angleCodeSeries] = frameDataRead_A(orgDataFilePath, frameRInd, prtNum)
+ * (MatlabProcess_xuzerui/frameDataRead_A_xzr.m:53-148; Show_Read.m:49-142 is the two-argument
+ * form that DMX_SignalProcessing_main_xzr.m:307 calls).  A record is 28 + 12 * point_prt + 8
+ * bytes: two uint16 sync words (0xA5A5, never checked by the reference), frameInd as two uint16
+ * (high word first), modFlag (uint16), beamPosNum, beamNums (uint8), freInd, prtInd (uint16), 10
+ * skipped bytes, two angle bytes with angleCode = (b26 + b27 * 2^7) * 360 / 16384 (2^7 as the
+ * reference writes it), then point_prt groups of 12 bytes [Ql Il Qr Ir] high, middle and low
+ * bytes, then an 8-byte tail.  A sample is hi * 2^16 + mid * 2^8 + lo, minus 2^24 if it is
+ * > 2^23 (:112-129): 0x800000 decodes to +8388608.  Left = I_l + j Q_l, Right = I_r + j Q_r.
+ * Output: d_out[f * frame_stride + b * beam_stride + prt * point_prt + s] as complex64, b = 0
+ * Left, 1 Right (strides in complex elements).  beam_stride = 0 means prt_num * point_prt and
+ * frame_stride = 0 means 2 * beam_stride: the dense [nframes][2][prt_num][point_prt] tensor
+ * that rsp_pc_mtd_cfar_diff_dev takes.  frame_stride = prt_num * point_prt with beam_stride =
+ * nframes * prt_num * point_prt gives two [nframes][prt_num][point_prt] stacks.  The 2 * nframes
+ * planes must not overlap: either beam_stride >= plane and frame_stride >= beam_stride + plane,
+ * or frame_stride >= plane and beam_stride >= (nframes - 1) * frame_stride + plane; other
+ * strides are refused.
+ * d_angle: float64 [nframes][prt_num] angleCode per PRT, nullable.
+ * d_head: int32 [nframes][prt_num][RSP_LEGACY_HEAD_FIELDS] = frameInd (its 32 bits), modFlag,
+ * beamPosNum, beamNums, freInd, prtInd, sync_ok (both sync words are 0xA5A5), 0; nullable.  The
+ * scalars frameDataRead_A returns are those of a frame's last PRT.
+ * d_status: int32 [nframes * prt_num + 1], a RSP_PRT_* code per row (rows are frame x PRT in
+ * stream order) and, last, the number of rows decoded.  RSP_PRT_TRUNCATED: the head or the
+ * payload is cut by nbytes; that row and every later one are written as zeros, with angle 0 and
+ * a zero head.  RSP_PRT_TAIL_TRUNCATED: only the 8 tail bytes are cut; the row is decoded (the
+ * reference stores the row before it skips the tail).
+ * Contract: d_stream is 4-byte aligned (the payload is read as dwords; a record is a multiple
+ * of 4 bytes), d_out and d_angle 8-byte aligned; prt_num, nframes <= 65535, point_prt <= 2^24.
+ * Arguments are checked before the context is touched (RSP_ERR_ARG with a message).  No context
+ * scratch is used: calls on different streams do not interfere. */
+typedef struct {
+    int32_t prt_num;     /* prtNum (1536) */
+    int32_t point_prt;   /* point_PRT (1031; 566 for the DMX waveform) */
+    int32_t nframes;     /* consecutive frames in d_stream, >= 1 */
+    int32_t reserved;    /* 0 */
+} rsp_legacy_ingest_params;
+
+enum { RSP_LEGACY_HEAD_FIELDS = 8 };  /* frameInd, modFlag, beamPosNum, beamNums, freInd, prtInd, sync_ok, 0 */
+
+/* Bytes of one record: 28 + 12 * point_prt + 8. */
+int rsp_legacy_record_bytes(const rsp_legacy_ingest_params* p, int64_t* bytes);
+int rsp_ingest_legacy_dev(rsp_ctx* ctx, const uint8_t* d_stream, int64_t nbytes,
+                          const rsp_legacy_ingest_params* p, void* d_out,
+                          int64_t beam_stride, int64_t frame_stride,
+                          double* d_angle, int32_t* d_head, int32_t* d_status, void* stream);
+
 /* ---- post-detection measurement --------------------------------------- */
 /* Range / velocity / elevation of every CFAR hit, replacing
  *   [rEstSeries, vEstSeries, eleAngleEstSeries] = motionParaMeasure(echo_MTD_sum, echo_MTD_diff,

@@ -1866,3 +1866,61 @@ int rsp_ingest_frame_dev(rsp_ctx* ctx, const uint8_t* d_stream, int64_t nbytes, 
     return ingest_run(ctx, "rsp_ingest_frame_dev", false, d_stream, nbytes, p, d_dbf, d_out, beam_stride, d_servo,
                       d_status, stream);
 }
+
+// ------------------------------------------------------------------ legacy two-beam 24-bit records
+static int legacy_shape(const char* who, const rsp_legacy_ingest_params* p, int64_t* rec) {
+    if (!p) return fail(nullptr, RSP_ERR_ARG, "%s: null params", who);
+    // a grid dimension per PRT and per frame; rows * rec_bytes stays far inside int64
+    if (p->prt_num < 1 || p->prt_num > 65535 || p->point_prt < 1 || p->point_prt > (1 << 24) || p->nframes < 1 ||
+        p->nframes > 65535 || p->reserved != 0 || (int64_t)p->prt_num * p->nframes > 0x7fffffff)
+        return fail(nullptr, RSP_ERR_ARG, "%s: bad shape (prt %d, point %d, frames %d, reserved %d)", who, p->prt_num,
+                    p->point_prt, p->nframes, p->reserved);
+    *rec = rsp::legacy_record_bytes(p->point_prt);
+    return RSP_OK;
+}
+
+int rsp_legacy_record_bytes(const rsp_legacy_ingest_params* p, int64_t* bytes) {
+    if (!bytes) return fail(nullptr, RSP_ERR_ARG, "rsp_legacy_record_bytes: null output");
+    return legacy_shape("rsp_legacy_record_bytes", p, bytes);
+}
+
+int rsp_ingest_legacy_dev(rsp_ctx* ctx, const uint8_t* d_stream, int64_t nbytes, const rsp_legacy_ingest_params* p,
+                          void* d_out, int64_t beam_stride, int64_t frame_stride, double* d_angle, int32_t* d_head,
+                          int32_t* d_status, void* stream) {
+    // everything is checked before the context is looked at (a malformed call is told apart without a GPU)
+    const char* who = "rsp_ingest_legacy_dev";
+    int64_t rec = 0;
+    const int rc = legacy_shape(who, p, &rec);
+    if (rc) return rc;
+    if (!d_stream || !d_out || !d_status) return fail(nullptr, RSP_ERR_ARG, "%s: null argument", who);
+    if (nbytes < 0) return fail(nullptr, RSP_ERR_ARG, "%s: negative byte count %lld", who, (long long)nbytes);
+    const int64_t plane = (int64_t)p->prt_num * p->point_prt, nf = p->nframes;
+    if (beam_stride == 0) beam_stride = plane;
+    if (frame_stride == 0) frame_stride = 2 * beam_stride;
+    // the 2 * nframes planes must not overlap: frames of [left, right] pairs, or two stacks of frames
+    const bool in_range = beam_stride > 0 && frame_stride > 0 && beam_stride <= ((int64_t)1 << 40) &&
+                          frame_stride <= ((int64_t)1 << 40);
+    const bool frame_major = in_range && beam_stride >= plane && (nf == 1 || frame_stride >= beam_stride + plane);
+    const bool beam_major = in_range && frame_stride >= plane && beam_stride >= (nf - 1) * frame_stride + plane;
+    if (!(frame_major || beam_major))
+        return fail(nullptr, RSP_ERR_ARG, "%s: planes of %lld elements overlap with beam_stride %lld, frame_stride %lld", who,
+                    (long long)plane, (long long)beam_stride, (long long)frame_stride);
+    // the payload is read as dwords (the record size is a multiple of 4); float2 / double stores
+    if ((uintptr_t)d_stream & 3) return fail(nullptr, RSP_ERR_ARG, "%s: d_stream must be 4-byte aligned", who);
+    if (((uintptr_t)d_out & 7) || ((uintptr_t)d_angle & 7) || ((uintptr_t)d_head & 3) || ((uintptr_t)d_status & 3))
+        return fail(nullptr, RSP_ERR_ARG, "%s: misaligned output (d_out, d_angle: 8 bytes; d_head, d_status: 4)", who);
+    if (!ctx) return fail(nullptr, RSP_ERR_ARG, "%s: null ctx", who);
+    if (!set_device(ctx)) return fail(ctx, RSP_ERR_HIP, "hipSetDevice failed");
+    rsp::LegacyIngestArgs a{};
+    a.prt_num = p->prt_num;
+    a.point_prt = p->point_prt;
+    a.nframes = p->nframes;
+    a.rows = (int64_t)p->prt_num * nf;
+    a.rec_bytes = rec;
+    a.nbytes = nbytes;
+    a.rows_decoded = rsp::legacy_rows_decoded(nbytes, rec, a.rows);
+    a.beam_stride = beam_stride;
+    a.frame_stride = frame_stride;
+    HIP_TRY(ctx, rsp::launch_ingest_legacy(d_stream, a, (float2*)d_out, d_angle, d_head, d_status, (hipStream_t)stream));
+    return RSP_OK;
+}

@@ -260,6 +260,28 @@ struct IngestArgs {
 hipError_t launch_ingest(const uint8_t* stream, int64_t nbytes, const IngestArgs& a, const float2* dbf,
                          float2* out, uint16_t* servo, int32_t* status, hipStream_t s);
 
+// Legacy two-beam 24-bit records (rsp_ingest_legacy.hip): frameDataRead_A_xzr.m / Show_Read.m.
+constexpr int kLegacyHeadBytes = 28, kLegacyGroupBytes = 12, kLegacyTailBytes = 8;
+constexpr int64_t legacy_record_bytes(int64_t point_prt) {
+    return kLegacyHeadBytes + kLegacyGroupBytes * point_prt + kLegacyTailBytes;
+}
+// Rows (frame x PRT, in stream order) whose head and payload lie inside nbytes: the reference
+// stores a row before it skips the tail, so a row with only its tail cut still counts.
+constexpr int64_t legacy_rows_decoded(int64_t nbytes, int64_t rec_bytes, int64_t rows) {
+    const int64_t n = (nbytes + kLegacyTailBytes) / rec_bytes;   // (r + 1) * rec - tail <= nbytes
+    return n < rows ? n : rows;
+}
+struct LegacyIngestArgs {
+    int prt_num, point_prt, nframes;
+    int64_t rows;                       // nframes * prt_num
+    int64_t rows_decoded;               // legacy_rows_decoded: rows from here on are zeros
+    int64_t rec_bytes, nbytes;
+    int64_t beam_stride, frame_stride;  // output elements between the two beams' planes / between frames
+};
+// status: int32 [rows + 1]; angle ([rows]) and head ([rows][RSP_LEGACY_HEAD_FIELDS]) may be null.
+hipError_t launch_ingest_legacy(const uint8_t* stream, const LegacyIngestArgs& a, float2* out, double* angle,
+                                int32_t* head, int32_t* status, hipStream_t s);
+
 // Payload bytes of one record by data type (FrameDataRead_xzr.m:104-119): ADC (0) int16 per
 // channel, DDC (1) int16 I/Q per channel, anything else the 24-bit DBF layout (3-byte I/Q per
 // channel plus 8 - mod(6*ch, 8) pad bytes per sample), the whole padded to 64 B.

@@ -33,7 +33,7 @@ EXPORTS = ("rsp_version", "rsp_create", "rsp_destroy", "rsp_last_error", "rsp_se
            "rsp_ingest_ddc_dev", "rsp_ingest_frame_dev", "rsp_motion_measure_dev", "rsp_prefilter_dev", "rsp_set_prefilter",
            "rsp_pc_mtd_cfar_f64", "rsp_cfar_f64", "rsp_set_range_concat", "rsp_score_dev", "rsp_score_summary",
            "rsp_set_pc_prune", "rsp_set_lane_chunks", "rsp_pc_plan", "rsp_scr_dev", "rsp_inject_dev", "rsp_scr_gain",
-           "rsp_cfar_plan")
+           "rsp_cfar_plan", "rsp_legacy_record_bytes", "rsp_ingest_legacy_dev")
 RSP_NKERNELS = 4
 KERNEL_NAMES = ("pc_kernel", "mtd_kernel", "cfar_r_kernel", "cfar_v_kernel")
 
@@ -73,6 +73,16 @@ class rsp_ingest_params(C.Structure):
     _fields_ = [("prt_num", C.c_int32), ("point_prt", C.c_int32), ("channel_num", C.c_int32),
                 ("beam_num", C.c_int32), ("bytes_head", C.c_int32), ("bytes_realtime", C.c_int32),
                 ("bytes_tail", C.c_int32)]
+
+
+class rsp_legacy_ingest_params(C.Structure):
+    _fields_ = [("prt_num", C.c_int32), ("point_prt", C.c_int32), ("nframes", C.c_int32), ("reserved", C.c_int32)]
+
+
+RSP_LEGACY_HEAD_FIELDS = 8
+# d_head columns of rsp_ingest_legacy_dev
+(RSP_LEGACY_FRAME_IND, RSP_LEGACY_MOD_FLAG, RSP_LEGACY_BEAM_POS_NUM, RSP_LEGACY_BEAM_NUMS, RSP_LEGACY_FRE_IND,
+ RSP_LEGACY_PRT_IND, RSP_LEGACY_SYNC_OK) = range(7)
 
 
 class rsp_measure_params(C.Structure):
@@ -210,6 +220,10 @@ def load_library(path=None):
     lib.rsp_ingest_ddc_dev.argtypes = [vp, vp, i64, C.POINTER(rsp_ingest_params), vp, vp, i64, vp, vp, vp]
     lib.rsp_ingest_frame_dev.restype = C.c_int
     lib.rsp_ingest_frame_dev.argtypes = [vp, vp, i64, C.POINTER(rsp_ingest_params), vp, vp, i64, vp, vp, vp]
+    lib.rsp_legacy_record_bytes.restype = C.c_int
+    lib.rsp_legacy_record_bytes.argtypes = [C.POINTER(rsp_legacy_ingest_params), C.POINTER(i64)]
+    lib.rsp_ingest_legacy_dev.restype = C.c_int
+    lib.rsp_ingest_legacy_dev.argtypes = [vp, vp, i64, C.POINTER(rsp_legacy_ingest_params), vp, i64, i64, vp, vp, vp, vp]
     lib.rsp_motion_measure_dev.restype = C.c_int
     lib.rsp_motion_measure_dev.argtypes = [vp, vp, vp, vp, i64, i64, i64, C.POINTER(rsp_measure_params), vp, vp,
                                            i64, vp, vp, vp, vp]

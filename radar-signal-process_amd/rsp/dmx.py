@@ -11,8 +11,13 @@ per-part target series:
     Measure.measure_dev over the column windows of the same device planes.
 
 Frames are batched ([batch][2 beams][P][R] complex64 on the device); everything between the
-echo and the estimates stays in HBM.  The reference's own frame reader (frameDataRead_A) is
-missing from the repository, so the echo matrices are the input here.
+echo and the estimates stays in HBM.  The frame reader the main calls at :307, frameDataRead_A,
+is MatlabProcess_xuzerui/Show_Read.m (two arguments, with the in-file frame seek) and
+frameDataRead_A_xzr.m (three arguments, the seek commented out); both are written for the
+legacy waveform's point_PRT = 1031.  No reader for this waveform's point_PRT = 566 (:111) ships
+in the reference: process_records_dev ASSUMES the same record layout with point_prt = 566
+(28-byte head, 12 bytes per sample, 8-byte tail) and decodes it on the GPU (rsp.ingest.LegacyIngest);
+process_dev takes the echo matrices themselves.
 """
 import math
 
@@ -25,7 +30,7 @@ from .measure import Measure, angle_KvalueGen, freValueGen
 # DMX_SignalProcessing_main_xzr.m:250-270
 DMX_DEFAULTS = dict(rSysErr_short=0.0, rSysErr_long=62.0 * 12.0, rMeasureErr_short=297.0, rMeasureErr_long=92.0,
                     extraDots=2, rInterpTimes=8, vInterpTimes=4, eleAngleComp=0.0, eleAngleSysErr=0.0,
-                    beamAngleStep=5.0, sysNum=1)
+                    beamAngleStep=5.0, sysNum=1, northAngle=29.01, angleE1=5.9)
 
 
 def dmx_scales(spec, freInd, **kw):
@@ -59,10 +64,13 @@ class DmxFrameProcessor:
         self.kValues = angle_KvalueGen(self.o["sysNum"])
         self.scales = dmx_scales(self.spec, self.freInd, **kw)
         self.device = self.meas.device
+        self._ingest = None
 
     def close(self):
         self.eng.close()
         self.meas.close()
+        if self._ingest is not None:
+            self._ingest.close()
 
     def process_dev(self, echo, beamPosNum, with_flagV=True, max_hits=4096):
         """echo: complex64 [batch][2][P][R] (left, right) on the device.  Returns a dict of
@@ -88,3 +96,41 @@ class DmxFrameProcessor:
             out[("long", fk)] = self.meas.measure_dev(out["sum"], out["diff"], out[fk], p, rL, vS,
                                                       max_hits=max_hits, cols=(ps, self.spec.R_out))
         return out
+
+    def process_records_dev(self, d_stream, nbytes, nframes, with_flagV=True, max_hits=4096):
+        """:307-310 + process_dev from the record bytes: d_stream holds nframes * P consecutive
+        legacy records (uint8 on the device, 4-byte aligned; the layout assumed for this waveform,
+        see the module docstring), decoded into [nframes][2][P][R] without leaving HBM.  As the main
+        does, each frame's beamPosNum and freInd are those of its last PRT; a frame whose freInd is
+        not this processor's raises ValueError (its scales and k value would be another
+        frequency's), and so does a stream that ends inside a frame.  The angle codes get
+        angleCode = rem(angleCode + northAngle + angleE1, 360) (:310) on the host.
+        process_dev measures a batch at one beam position, so the frames are processed in runs of
+        consecutive frames that share beamPosNum.  Returns a list with one dict per run:
+        process_dev's outputs for the run's frames plus 'frames' (first, end), 'beamPosNum',
+        'frameInd' (int64 [n]) and 'angleCode' (float64 [n][P], host)."""
+        from . import _capi as capi
+        from .ingest import LegacyIngest
+        if self._ingest is None:
+            self._ingest = LegacyIngest(self.device.index or 0)
+        P, R, F = self.spec.P, self.spec.R, int(nframes)
+        echo, angle, head, status = self._ingest.decode_dev(d_stream, nbytes, P, R, F)
+        decoded = int(status[F * P].item())
+        if decoded < F * P:
+            raise ValueError("process_records_dev: the stream ends inside PRT %d of frame %d" % (decoded % P + 1, decoded // P))
+        last = head[:, P - 1].cpu().numpy()
+        fre = last[:, capi.RSP_LEGACY_FRE_IND]
+        if np.any(fre != self.freInd):
+            f = int(np.flatnonzero(fre != self.freInd)[0])
+            raise ValueError("process_records_dev: frame %d has freInd %d, this processor's is %d" % (f, int(fre[f]), self.freInd))
+        bpn = last[:, capi.RSP_LEGACY_BEAM_POS_NUM]
+        frame_ind = last[:, capi.RSP_LEGACY_FRAME_IND].astype(np.int64) & 0xffffffff
+        code = np.fmod(angle.cpu().numpy() + self.o["northAngle"] + self.o["angleE1"], 360.0)
+        runs, a = [], 0
+        for b in range(1, F + 1):
+            if b == F or bpn[b] != bpn[a]:
+                out = self.process_dev(echo[a:b], int(bpn[a]), with_flagV=with_flagV, max_hits=max_hits)
+                out.update(frames=(a, b), beamPosNum=int(bpn[a]), frameInd=frame_ind[a:b], angleCode=code[a:b])
+                runs.append(out)
+                a = b
+        return runs

@@ -14,6 +14,17 @@ Mirrors the reference's reader stack with the same names and argument meaning:
     the chain's layout [beam][prt][sample] (MATLAB's is prt x sample x beam: .permute(1, 2, 0)).
   * read_dbf_coeffs(path)                                bin_to_mat_xzr.m:22-29
 
+and, for the legacy two-beam 24-bit capture format (the reader of bin_to_mat_xzr.m:14, main_cfar.m
+and DMX_SignalProcessing_main_xzr.m:307):
+  * dataFullPathGen(path, fileInd)                       MatlabProcess_xuzerui/dataFullPathGen.m
+    (00000k.bin: not the 1.00000k.bin of DataFullPathGen.m above)
+  * LegacyIngest.frameDataRead_A(orgDataFilePath, frameRInd, prtNum)
+        -> (echoData_Frame_Left, echoData_Frame_Right, frameInd, modFlag, beamPosNum, beamNums,
+            freInd, angleCodeSeries)
+    frameDataRead_A_xzr.m:15-150 and, with frame_seek=True, Show_Read.m:1-142; the decode runs on
+    the GPU (rsp_ingest_legacy_dev, csrc/rsp_ingest_legacy.hip), the host only reads the frame's
+    bytes and uploads them.
+
 The host reads each record as the reference does (head, realtime block, payload sized by the
 head, tail, each one read through the stream and stopping where the reference returns, so the
 stream position and file-boundary behaviour match) into one buffer per frame; the GPU then
@@ -268,3 +279,146 @@ class Ingest:
         # every early return of the reference sets is_global_stream_end (:62-189); a
         # completed frame returns (true, false) (:201-202)
         return out, angles, bool(completed), bool(not completed)
+
+
+# ---------------------------------------------------------------- legacy two-beam 24-bit records
+LEGACY_FRAMES_EACH_FILE = 10      # framesEachFile (frameDataRead_A_xzr.m:34)
+
+
+def dataFullPathGen(DataFilePath, fileInd):  # noqa: N802,N803 (reference name)
+    """MatlabProcess_xuzerui/dataFullPathGen.m:3-11."""
+    if fileInd < 10:
+        name = "00000" + str(fileInd) + ".bin"
+    elif fileInd < 100:
+        name = "0000" + str(fileInd) + ".bin"
+    else:
+        name = "000" + str(fileInd) + ".bin"
+    return os.path.join(DataFilePath, name)
+
+
+def legacy_record_bytes(point_PRT=1031):  # noqa: N803
+    """bytesTotalEachPRT (:27-31): 24 + 8 + 12 * point_PRT + 4."""
+    return 24 + 8 + 12 * int(point_PRT) + 4
+
+
+def legacy_file_index(frameRInd):  # noqa: N803
+    """fileInd = fix((frameRInd-1)/framesEachFile)+1 (:40); fix rounds towards zero."""
+    return int((int(frameRInd) - 1) / LEGACY_FRAMES_EACH_FILE) + 1
+
+
+def legacy_frame_skip(frameRInd):  # noqa: N803
+    """frameSkip = rem(frameRInd-1, framesEachFile) (:46): rem keeps the dividend's sign."""
+    return int(np.fmod(int(frameRInd) - 1, LEGACY_FRAMES_EACH_FILE))
+
+
+def legacy_frame_bytes(orgDataFilePath, frameRInd, prtNum=1536, point_PRT=1031, frame_seek=False):  # noqa: N803
+    """The bytes frameDataRead_A's PRT loop reads: prtNum records of the file that holds frame
+    frameRInd, from the file's start (frameDataRead_A_xzr.m:48 has its fseek commented out, so
+    that variant always reads the file's FIRST frame) or, frame_seek=True, from
+    bytesTotalEachFrame * frameSkip (Show_Read.m:45).  A negative offset (frameRInd = 0) makes
+    MATLAB's fseek fail without moving: the read starts at 0.  A short file gives fewer bytes."""
+    n = legacy_record_bytes(point_PRT) * int(prtNum)
+    with open(dataFullPathGen(orgDataFilePath, legacy_file_index(frameRInd)), "rb") as f:
+        if frame_seek:
+            skip = legacy_frame_skip(frameRInd)
+            if skip > 0:
+                f.seek(n * skip)
+        return f.read(n)
+
+
+class LegacyIngest:
+    """GPU decoder of the legacy two-beam 24-bit PRT records (rsp_ingest_legacy_dev)."""
+
+    def __init__(self, device=0):
+        import torch
+        self.lib = capi.load_library()
+        self.device = torch.device("cuda", device)
+        ctx = C.c_void_p()
+        capi.check(self.lib.rsp_create(C.byref(ctx), int(device), None), None)
+        self.ctx = ctx
+
+    def close(self):
+        if getattr(self, "ctx", None):
+            self.lib.rsp_destroy(self.ctx)
+            self.ctx = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @staticmethod
+    def params(prt_num, point_prt, nframes=1):
+        p = capi.rsp_legacy_ingest_params()
+        p.prt_num, p.point_prt, p.nframes, p.reserved = int(prt_num), int(point_prt), int(nframes), 0
+        return p
+
+    def record_bytes(self, point_prt=1031):
+        n = C.c_int64()
+        capi.check(self.lib.rsp_legacy_record_bytes(C.byref(self.params(1, point_prt)), C.byref(n)), None)
+        return n.value
+
+    def decode_dev(self, d_stream, nbytes, prt_num, point_prt, nframes=1, out=None, layout="frame_major",
+                   beam_stride=0, frame_stride=0, stream=None):
+        """nframes * prt_num consecutive records in d_stream (uint8 on the device, 4-byte aligned)
+        -> (out, angle float64 [nframes][prt_num], head int32 [nframes][prt_num][8], status int32
+        [nframes * prt_num + 1]), all on the device.  layout "frame_major": out is
+        [nframes][2][prt_num][point_prt] complex64 (what DmxFrameProcessor.process_dev takes);
+        "beam_major": [2][nframes][prt_num][point_prt] (a [batch][P][R] stack per beam for the
+        one-beam engine).  With `out` given, beam_stride / frame_stride (complex elements) place the
+        planes in it; 0 means the layout's dense strides."""
+        import torch
+        P, R, F = int(prt_num), int(point_prt), int(nframes)
+        if layout not in ("frame_major", "beam_major"):
+            raise ValueError("layout must be 'frame_major' or 'beam_major'")
+        if layout == "beam_major":
+            beam_stride = beam_stride or F * P * R
+            frame_stride = frame_stride or P * R
+        if out is None:
+            shape = (F, 2, P, R) if layout == "frame_major" else (2, F, P, R)
+            out = torch.empty(shape, dtype=torch.complex64, device=self.device)
+            beam_stride, frame_stride = (0, 0) if layout == "frame_major" else (F * P * R, P * R)
+        else:
+            bs, fs = beam_stride or P * R, frame_stride or 2 * (beam_stride or P * R)
+            if out.dtype != torch.complex64 or not out.is_contiguous() or out.device != self.device:
+                raise ValueError("out must be a contiguous complex64 tensor on the decoder's device")
+            if (F - 1) * fs + bs + P * R > out.numel():
+                raise ValueError("out holds %d elements, the strides need %d" % (out.numel(), (F - 1) * fs + bs + P * R))
+        angle = torch.empty((F, P), dtype=torch.float64, device=self.device)
+        head = torch.empty((F, P, capi.RSP_LEGACY_HEAD_FIELDS), dtype=torch.int32, device=self.device)
+        status = torch.empty((F * P + 1,), dtype=torch.int32, device=self.device)
+        s = stream if stream is not None else torch.cuda.current_stream(self.device)
+        capi.check(self.lib.rsp_ingest_legacy_dev(
+            self.ctx, C.c_void_p(d_stream.data_ptr()), int(nbytes), C.byref(self.params(P, R, F)),
+            C.c_void_p(out.data_ptr()), int(beam_stride), int(frame_stride), C.c_void_p(angle.data_ptr()),
+            C.c_void_p(head.data_ptr()), C.c_void_p(status.data_ptr()), C.c_void_p(s.cuda_stream)), self.ctx)
+        return out, angle, head, status
+
+    def upload(self, data):
+        """Record bytes -> a uint8 device tensor (torch's allocations are aligned far past 4 bytes)."""
+        import torch
+        return torch.frombuffer(bytearray(data) if len(data) else bytearray(4), dtype=torch.uint8).to(self.device)
+
+    def frameDataRead_A(self, orgDataFilePath, frameRInd, prtNum=1536, point_PRT=1031, frame_seek=False):  # noqa: N802,N803
+        """frameDataRead_A(orgDataFilePath, frameRInd, prtNum) -> (echoData_Frame_Left,
+        echoData_Frame_Right, frameInd, modFlag, beamPosNum, beamNums, freInd, angleCodeSeries):
+        Left / Right complex64 [prtNum][point_PRT] on the device (the reference's doubles hold
+        integers of magnitude <= 2^23, exact in fp32), the head scalars of the last PRT read,
+        angleCodeSeries float64 [prtNum] (host).
+        frame_seek=False is frameDataRead_A_xzr.m, whose in-file seek (:48) is commented out: it
+        returns the FIRST frame of the file that holds frameRInd, whatever frameRInd's place in
+        that file.  frame_seek=True is Show_Read.m (:45), the reader the DMX main calls; its
+        eighth output is the scalar angleCode of the last PRT, angleCodeSeries[-1] here.
+        (Show_Read.m:17,32 overwrite its own arguments with a path and frame 25; that is not
+        reproduced.)  A file too short for prtNum records raises, where MATLAB's assignment of an
+        empty fread does."""
+        data = legacy_frame_bytes(orgDataFilePath, frameRInd, prtNum, point_PRT, frame_seek)
+        out, angle, head, status = self.decode_dev(self.upload(data), len(data), prtNum, point_PRT, 1)
+        decoded = int(status[prtNum].item())
+        if decoded < prtNum:
+            raise ValueError("frameDataRead_A: the file ends inside PRT %d of %d" % (decoded + 1, prtNum))
+        h = head[0, prtNum - 1].cpu().numpy()
+        frameInd = int(h[capi.RSP_LEGACY_FRAME_IND]) & 0xffffffff     # frameInd1 * 2^16 + frameInd2 is unsigned
+        return (out[0, 0], out[0, 1], frameInd, int(h[capi.RSP_LEGACY_MOD_FLAG]), int(h[capi.RSP_LEGACY_BEAM_POS_NUM]),
+                int(h[capi.RSP_LEGACY_BEAM_NUMS]), int(h[capi.RSP_LEGACY_FRE_IND]), angle[0].cpu().numpy())
