@@ -554,6 +554,56 @@ int rsp_motion_measure_dev(rsp_ctx* ctx, const float* d_sum, const float* d_diff
                            const double* d_r_scale, const double* d_v_scale, int64_t max_hits,
                            double* d_est, int32_t* d_cells /* nullable */, int32_t* d_count, void* stream);
 
+/* ---- plot condensation: one peak cell per cluster of CFAR hits -------------------------- */
+/* The reference scatters one estimate per CFAR hit (DMX_SignalProcessing_main_xzr.m:530-558); the
+ * local-peak gates that would thin them are commented out (Function_CFAR1D_sub.m, _fixCells.m:60-83).
+ * rsp_condense_dev labels the connected hits of each CPI's V x R flag window and keeps each
+ * cluster's ("plot's") strongest cell.
+ *
+ * Adjacency: hits (v1, r1), (v2, r2) are adjacent when dv <= gap_v and |r1 - r2| <= gap_r, with
+ * dv = |v1 - v2|, or min(|v1 - v2|, V - |v1 - v2|) with wrap_v (the Doppler axis is periodic: a
+ * target at the folding velocity straddles rows 0 and V-1 of an fftshifted RDM).  gap 1, 1 is
+ * 8-connectivity; 0, 0 makes every hit its own plot.  A plot is a connected component of the
+ * transitive closure.  Hits never join across the window's column edges.
+ * Peak: the plot's hit with the largest amplitude, compared as float32 values; on equal
+ * amplitudes the first in MATLAB's find() order (the smallest r*V + v), the tie rule of
+ * executeCFAR.m:69-70.  Amplitudes at flagged cells are magnitudes: where one is negative or NaN
+ * the choice of peak is unspecified.
+ *
+ * d_amp: float32, d_flag: uint8 (nonzero = hit), d_peak: uint8, all [batch][V][ld] windows of the
+ * same geometry (cp->ld, cp->cpi_stride).  Per CPI:
+ *   d_peak   1 at each plot's peak cell, 0 at every other cell of the window: every cell of the
+ *            window is written (the caller clears nothing; cells outside the window's columns
+ *            are not touched), also when d_plots overflows.  rsp_motion_measure_dev takes it as
+ *            its d_flag: hit i of that measurement is plot i.
+ *   d_plots  int32 [batch][max_plots][8] or NULL: {peak_v, peak_r, n_cells, v_min, v_max, r_min,
+ *            r_max, 0}, 0-based and relative to the window, ordered by the peak's find() order.
+ *            v_min / v_max are the plain minimum and maximum of the row indices: a plot joined
+ *            across the seam by wrap_v reports 0 and V-1.  Plots past max_plots are counted, not
+ *            written, and the rest of d_plots is left untouched.
+ *   d_count  int32 [batch][2] = {n_plots, n_hits}.
+ * Every combination across threads is an integer atomic (min, max, add) whose result does not
+ * depend on the order of arrival: two runs give the same bytes, and a CPI gives the same bytes
+ * alone as inside a batch.
+ * Memory: the context's grow-only condensation pool holds, per CPI of a chunk, 16 B per cell of
+ * the window (an int32 label, a 64-bit peak key and an int32 hit-list slot, each touched at
+ * flagged cells only) + 24 B x min(max_plots, V*R) + 16 B; 2048 x 512 with max_plots 4096:
+ * 16.1 MiB per CPI, 4.0 GiB at batch 256.  The pool grows to batch x that and is capped at 8 GiB
+ * (one CPI where a CPI needs more): a batch that needs more runs as consecutive chunks of
+ * floor(8 GiB / bytes per CPI) CPIs on the stream (509 CPIs at 2048 x 512).
+ * Asynchronous on `stream`; works on any context, the CFAR-only kind included. */
+typedef struct {
+    int32_t gap_v, gap_r;   /* 0..4 each */
+    int32_t wrap_v;         /* 0/1; 1 needs V > 2*gap_v */
+    int32_t reserved;       /* 0 */
+    int64_t ld;             /* row pitch in elements (0 = R), as rsp_measure_params.ld */
+    int64_t cpi_stride;     /* elements between CPIs (0 = V * ld) */
+} rsp_condense_params;
+
+int rsp_condense_dev(rsp_ctx* ctx, const float* d_amp, const uint8_t* d_flag, int64_t V, int64_t R,
+                     int64_t batch, const rsp_condense_params* cp, uint8_t* d_peak,
+                     int32_t max_plots, int32_t* d_plots /* nullable */, int32_t* d_count, void* stream);
+
 /* ---- detection scoring against truth (main_cfar.m's evaluation functions) ---------------- */
 /* The four local functions at the end of MatlabProcess_xuzerui/CFAR_WangCai/main_cfar.m, the
  * reason for its `for T=[5]` threshold loop (:40), over a device-resident batch of flag matrices:

@@ -221,7 +221,7 @@ int rsp_destroy(rsp_ctx* ctx) {
     for (void* p : ctx->owned) hipFree(p);
     DevBuf* bufs[] = {&ctx->pf_gain, &ctx->scratch_pc, &ctx->cat_tmp, &ctx->tmp_flagV, &ctx->tmp_rdm, &ctx->hit_list, &ctx->hit_ctr,
                       &ctx->st_in, &ctx->st_canon, &ctx->st_rdm, &ctx->st_flag, &ctx->st_flagV, &ctx->st_t,
-                      &ctx->meas_band, &ctx->ing_meta, &ctx->scr_ps};
+                      &ctx->meas_band, &ctx->ing_meta, &ctx->scr_ps, &ctx->cond_tmp};
     for (DevBuf* b : bufs)
         if (b->p) hipFree(b->p);
     for (auto& e : ctx->evs) {
@@ -1548,6 +1548,67 @@ int rsp_motion_measure_dev(rsp_ctx* ctx, const float* d_sum, const float* d_diff
     HIP_TRY(ctx, rsp::launch_measure(d_sum, d_diff, d_flag, (int)V, (int)R, (int)batch, a, d_r_scale, d_v_scale,
                                      max_hits, d_est, d_cells, d_count, (int32_t*)ctx->meas_band.p, nb,
                                      (hipStream_t)stream));
+    return scratch_release(ctx, (hipStream_t)stream);
+}
+
+// ------------------------------------------------------------------ plot condensation
+// Scratch budget of one chunk of CPIs: a larger batch runs as consecutive chunks on the stream.
+// Chunks are kept large because the peaks' hit list costs one workgroup's scan of a whole plane
+// per launch, whatever the number of CPIs in it (2048 x 512 at batch 256: 5 chunks under a 1 GiB
+// budget took 3.5 ms, of which 3 ms were the five hit lists).
+static constexpr size_t kCondenseChunkBytes = (size_t)8 << 30;
+
+int rsp_condense_dev(rsp_ctx* ctx, const float* d_amp, const uint8_t* d_flag, int64_t V, int64_t R, int64_t batch,
+                     const rsp_condense_params* cp, uint8_t* d_peak, int32_t max_plots, int32_t* d_plots,
+                     int32_t* d_count, void* stream) {
+    // everything that can be checked on the host comes before the context is looked at
+    if (!cp || !d_amp || !d_flag || !d_peak || !d_count)
+        return fail(ctx, RSP_ERR_ARG, "rsp_condense_dev: null argument");
+    if (cp->gap_v < 0 || cp->gap_v > 4 || cp->gap_r < 0 || cp->gap_r > 4)
+        return fail(ctx, RSP_ERR_ARG, "rsp_condense_dev: gap %d, %d outside 0..4", cp->gap_v, cp->gap_r);
+    if ((cp->wrap_v != 0 && cp->wrap_v != 1) || cp->reserved != 0)
+        return fail(ctx, RSP_ERR_ARG, "rsp_condense_dev: wrap_v %d / reserved %d", cp->wrap_v, cp->reserved);
+    if (V < 1 || R < 1 || batch < 0 || batch > 0x7fffffff || max_plots < 0)
+        return fail(ctx, RSP_ERR_ARG, "rsp_condense_dev: bad shape %lld x %lld x %lld, max_plots %d", (long long)batch,
+                    (long long)V, (long long)R, max_plots);
+    if (cp->wrap_v && V <= 2 * (int64_t)cp->gap_v)
+        return fail(ctx, RSP_ERR_ARG, "rsp_condense_dev: wrap_v needs V > 2*gap_v (V = %lld, gap_v = %d)", (long long)V,
+                    cp->gap_v);
+    if (V > ((int64_t)1 << 31) || R > ((int64_t)1 << 31) || V * R >= (int64_t)1 << 31)
+        return fail(ctx, RSP_ERR_UNSUPPORTED, "rsp_condense_dev: %lld x %lld cells (the cell index is int32)",
+                    (long long)V, (long long)R);
+    const int64_t ld = cp->ld ? cp->ld : R, cs = cp->cpi_stride ? cp->cpi_stride : V * ld;
+    if (ld < R || cs < (V - 1) * ld + R)
+        return fail(ctx, RSP_ERR_ARG, "rsp_condense_dev: row pitch %lld / CPI stride %lld too small for %lld x %lld",
+                    (long long)ld, (long long)cs, (long long)V, (long long)R);
+    if ((const uint8_t*)d_peak == d_flag) return fail(ctx, RSP_ERR_ARG, "rsp_condense_dev: d_peak == d_flag");
+    if (!ctx) return fail(nullptr, RSP_ERR_ARG, "rsp_condense_dev: null ctx");
+    if (batch == 0) return RSP_OK;
+    if (!set_device(ctx)) return fail(ctx, RSP_ERR_HIP, "hipSetDevice failed");
+    rsp::CondenseArgs a{};
+    a.V = (int)V;
+    a.R = (int)R;
+    a.gap_v = cp->gap_v;
+    a.gap_r = cp->gap_r;
+    a.wrap_v = cp->wrap_v;
+    a.max_plots = max_plots;
+    a.ld = ld;
+    a.cs = cs;
+    a.cells = (size_t)V * (size_t)R;
+    const size_t per = rsp::condense_scratch_per_cpi(V, R, d_plots ? max_plots : 0);
+    int64_t chunk = (int64_t)(kCondenseChunkBytes / per);
+    chunk = chunk < 1 ? 1 : (chunk > 32768 ? 32768 : chunk);
+    if (chunk > batch) chunk = batch;
+    int rc = scratch_acquire(ctx, (hipStream_t)stream);
+    if (rc) return rc;
+    rc = ensure(ctx, ctx->cond_tmp, (size_t)chunk * per);
+    if (rc != RSP_OK) return rc;
+    for (int64_t b0 = 0; b0 < batch; b0 += chunk) {
+        const int64_t nb = batch - b0 < chunk ? batch - b0 : chunk;
+        HIP_TRY(ctx, rsp::launch_condense(d_amp + b0 * cs, d_flag + b0 * cs, d_peak + b0 * cs, (int)nb, a,
+                                          d_plots ? d_plots + b0 * (int64_t)max_plots * 8 : nullptr, d_count + b0 * 2,
+                                          ctx->cond_tmp.p, (hipStream_t)stream));
+    }
     return scratch_release(ctx, (hipStream_t)stream);
 }
 

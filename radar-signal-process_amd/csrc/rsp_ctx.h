@@ -69,6 +69,7 @@ struct rsp_ctx {
     DevBuf hit_ctr;                     // per-lane, per-MTD-workgroup hit counts
     DevBuf meas_band;                   // measurement: per-(CPI, band, column) hit counts
     DevBuf scr_ps;                      // injection: per-CPI sums, ratios and pulse phases (InjectArgs::ps)
+    DevBuf cond_tmp;                    // condensation: labels, keys and hit lists of one chunk of CPIs
     DevBuf ing_meta;                    // ingest: per-PRT record offsets and types
     DevBuf st_in, st_canon, st_rdm, st_flag, st_flagV, st_t;  // host-API staging (rsp_cfar)
     // Pipelined host-buffer path (rsp_pc_mtd_cfar / rsp_pc_mtd): chunk k's H2D (copy stream),

@@ -168,6 +168,27 @@ hipError_t launch_measure(const float* sum, const float* diff, const uint8_t* fl
                           const MeasureArgs& a, const double* r_scale, const double* v_scale, int64_t max_hits,
                           double* est, int32_t* cells, int32_t* count, int32_t* band_cnt, int nb, hipStream_t st);
 
+// The hit list alone (hits_kernel): list[(cpi * max_hits + i) * 3] = cell v*R + c of hit i in find()
+// order (the other two words of a slot are not written), count[cpi * 2] = the CPI's hits.
+hipError_t launch_hit_list(const uint8_t* flag, int V, int R, int batch, int64_t ld, int64_t cs, int64_t max_hits,
+                           int64_t* list, int32_t* count, hipStream_t st);
+
+// Plot condensation (rsp_condense.hip): rsp_condense_params with the shape and the resolved pitches.
+struct CondenseArgs {
+    int V, R;
+    int gap_v, gap_r, wrap_v;
+    int max_plots;    // records per CPI in d_plots
+    int list_cap;     // (launch_condense) slots per CPI of the peaks' hit list
+    int tw;           // (launch_condense) 16-column segments per row of a dense tile
+    int64_t ld, cs;   // row pitch and CPI stride of the amplitude / flag / peak planes, in elements
+    size_t cells;     // V * R
+};
+// Scratch bytes per CPI of a launch_condense chunk (a multiple of 16).
+size_t condense_scratch_per_cpi(int64_t V, int64_t R, int32_t max_plots);
+// One chunk of CPIs (at most 65535); plots may be null; scratch holds batch * condense_scratch_per_cpi bytes.
+hipError_t launch_condense(const float* amp, const uint8_t* flag, uint8_t* peak, int batch, CondenseArgs a,
+                           int32_t* plots, int32_t* count, void* scratch, hipStream_t st);
+
 // Detection scoring (rsp_score.hip): rsp_score_params with the shape and the resolved pitches.
 struct ScoreArgs {
     int V, R;

@@ -579,6 +579,25 @@ int measure_bands(int V, int batch) {
     return want < max_nb ? want : max_nb;
 }
 
+hipError_t launch_hit_list(const uint8_t* flag, int V, int R, int batch, int64_t ld, int64_t cs, int64_t max_hits,
+                           int64_t* list, int32_t* count, hipStream_t st) {
+    if (batch <= 0) return hipSuccess;
+    // launch_e's choice of instance for one workgroup per CPI; E and mtd0_num only classify the
+    // hits past max_hits, which no caller of the list reads
+    const bool wide = R % 16 == 0 && R >= 16 * 16 && ld % 16 == 0 && cs % 16 == 0 && ((uintptr_t)flag & 15) == 0;
+    int G = wide ? 16 : 64;
+    const int groups = wide ? R / 16 : R;
+    while (G < groups && G < kThreads) G <<= 1;
+    double* est = reinterpret_cast<double*>(list);
+    if (wide)
+        hipLaunchKernelGGL((hits_kernel<1, 16>), dim3(batch), dim3(kThreads), 0, st, flag, V, R, G, ld, cs, 0, max_hits,
+                           est, count);
+    else
+        hipLaunchKernelGGL((hits_kernel<1, 1>), dim3(batch), dim3(kThreads), 0, st, flag, V, R, G, ld, cs, 0, max_hits,
+                           est, count);
+    return hipGetLastError();
+}
+
 hipError_t launch_measure(const float* sum, const float* diff, const uint8_t* flag, int V, int R, int batch,
                           const MeasureArgs& a, const double* r_scale, const double* v_scale, int64_t max_hits,
                           double* est, int32_t* cells, int32_t* count, int32_t* band_cnt, int nb, hipStream_t st) {

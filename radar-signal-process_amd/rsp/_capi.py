@@ -33,7 +33,7 @@ EXPORTS = ("rsp_version", "rsp_create", "rsp_destroy", "rsp_last_error", "rsp_se
            "rsp_ingest_ddc_dev", "rsp_ingest_frame_dev", "rsp_motion_measure_dev", "rsp_prefilter_dev", "rsp_set_prefilter",
            "rsp_pc_mtd_cfar_f64", "rsp_cfar_f64", "rsp_set_range_concat", "rsp_score_dev", "rsp_score_summary",
            "rsp_set_pc_prune", "rsp_set_lane_chunks", "rsp_pc_plan", "rsp_scr_dev", "rsp_inject_dev", "rsp_scr_gain",
-           "rsp_cfar_plan", "rsp_legacy_record_bytes", "rsp_ingest_legacy_dev")
+           "rsp_cfar_plan", "rsp_legacy_record_bytes", "rsp_ingest_legacy_dev", "rsp_condense_dev")
 RSP_NKERNELS = 4
 KERNEL_NAMES = ("pc_kernel", "mtd_kernel", "cfar_r_kernel", "cfar_v_kernel")
 
@@ -91,6 +91,11 @@ class rsp_measure_params(C.Structure):
                 ("delta_v", C.c_double), ("k_value", C.c_double), ("beam_angle_step", C.c_double),
                 ("ele_comp", C.c_double), ("ele_sys_err", C.c_double), ("ld", C.c_int64),
                 ("cpi_stride", C.c_int64)]
+
+
+class rsp_condense_params(C.Structure):
+    _fields_ = [("gap_v", C.c_int32), ("gap_r", C.c_int32), ("wrap_v", C.c_int32), ("reserved", C.c_int32),
+                ("ld", C.c_int64), ("cpi_stride", C.c_int64)]
 
 
 class rsp_score_params(C.Structure):
@@ -227,6 +232,8 @@ def load_library(path=None):
     lib.rsp_motion_measure_dev.restype = C.c_int
     lib.rsp_motion_measure_dev.argtypes = [vp, vp, vp, vp, i64, i64, i64, C.POINTER(rsp_measure_params), vp, vp,
                                            i64, vp, vp, vp, vp]
+    lib.rsp_condense_dev.restype = C.c_int
+    lib.rsp_condense_dev.argtypes = [vp, vp, vp, i64, i64, i64, C.POINTER(rsp_condense_params), vp, i32, vp, vp, vp]
     lib.rsp_score_dev.restype = C.c_int
     lib.rsp_score_dev.argtypes = [vp, vp, vp, i64, i64, i64, C.POINTER(rsp_score_params), vp, vp, vp]
     lib.rsp_score_summary.restype = C.c_int

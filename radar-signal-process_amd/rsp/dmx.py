@@ -65,17 +65,28 @@ class DmxFrameProcessor:
         self.scales = dmx_scales(self.spec, self.freInd, **kw)
         self.device = self.meas.device
         self._ingest = None
+        self._cond = None
 
     def close(self):
         self.eng.close()
         self.meas.close()
+        if self._cond is not None:
+            self._cond.close()
         if self._ingest is not None:
             self._ingest.close()
 
-    def process_dev(self, echo, beamPosNum, with_flagV=True, max_hits=4096):
+    def process_dev(self, echo, beamPosNum, with_flagV=True, max_hits=4096, condense=None):
         """echo: complex64 [batch][2][P][R] (left, right) on the device.  Returns a dict of
         device outputs: the planes (sum, diff, flag, flagV) and, per part ('short', 'long') and
-        flag kind ('flag', 'flagV'), (est, cells, count) as Measure.measure_dev gives them."""
+        flag kind ('flag', 'flagV'), (est, cells, count) as Measure.measure_dev gives them.
+
+        condense = dict(gap=(gv, gr), wrap_v=False): the flags of each part and kind are first
+        condensed into plots (Condense.condense_dev over the same column windows, amplitudes from
+        the sum plane) and the measurement runs on the peak planes, one estimate per plot:
+        out[(part, kind)] is the measurement of the peaks, out[(part, kind, 'plots')] =
+        (plots, count) of the condensation (at most max_hits records per CPI), out['peak'] /
+        out['peakV'] the peak planes.  wrap_v defaults to False: this layout has no fftshift, and
+        its seam lies in the zeroed zero-velocity band."""
         import torch
         B = echo.shape[0]
         shp = (B, self.spec.V, self.spec.R_out)
@@ -90,6 +101,8 @@ class DmxFrameProcessor:
         p = self.meas.params(o["extraDots"], dR, o["rInterpTimes"], dV, o["vInterpTimes"], k_value, beamPosNum,
                              o["beamAngleStep"], o["eleAngleComp"], o["eleAngleSysErr"], self.spec.radar["M0"])
         ps = self.spec.cfar_segments[0][1]
+        if condense is not None:
+            return self._measure_plots(out, p, ps, with_flagV, max_hits, dict(condense))
         for fk in ("flag", "flagV") if with_flagV else ("flag",):
             out[("short", fk)] = self.meas.measure_dev(out["sum"], out["diff"], out[fk], p, rS, vS,
                                                        max_hits=max_hits, cols=(0, ps))
@@ -97,7 +110,26 @@ class DmxFrameProcessor:
                                                       max_hits=max_hits, cols=(ps, self.spec.R_out))
         return out
 
-    def process_records_dev(self, d_stream, nbytes, nframes, with_flagV=True, max_hits=4096):
+    def _measure_plots(self, out, p, ps, with_flagV, max_hits, cond):
+        import torch
+        from .condense import Condense
+        if self._cond is None:
+            self._cond = Condense(self.device.index or 0)
+        gap, wrap_v = cond.pop("gap", (1, 1)), cond.pop("wrap_v", False)
+        if cond:
+            raise TypeError("process_dev: condense takes gap and wrap_v, not %s" % sorted(cond))
+        rS, rL, vS = self.scales[:3]
+        for fk, pk in (("flag", "peak"), ("flagV", "peakV")) if with_flagV else (("flag", "peak"),):
+            out[pk] = torch.empty_like(out[fk])
+            for part, cols, rs in (("short", (0, ps), rS), ("long", (ps, self.spec.R_out), rL)):
+                _, plots, count = self._cond.condense_dev(out["sum"], out[fk], gap=gap, wrap_v=wrap_v,
+                                                          max_plots=max_hits, cols=cols, peak=out[pk])
+                out[(part, fk, "plots")] = (plots, count)
+                out[(part, fk)] = self.meas.measure_dev(out["sum"], out["diff"], out[pk], p, rs, vS,
+                                                        max_hits=max_hits, cols=cols)
+        return out
+
+    def process_records_dev(self, d_stream, nbytes, nframes, with_flagV=True, max_hits=4096, condense=None):
         """:307-310 + process_dev from the record bytes: d_stream holds nframes * P consecutive
         legacy records (uint8 on the device, 4-byte aligned; the layout assumed for this waveform,
         see the module docstring), decoded into [nframes][2][P][R] without leaving HBM.  As the main
@@ -108,7 +140,7 @@ class DmxFrameProcessor:
         process_dev measures a batch at one beam position, so the frames are processed in runs of
         consecutive frames that share beamPosNum.  Returns a list with one dict per run:
         process_dev's outputs for the run's frames plus 'frames' (first, end), 'beamPosNum',
-        'frameInd' (int64 [n]) and 'angleCode' (float64 [n][P], host)."""
+        'frameInd' (int64 [n]) and 'angleCode' (float64 [n][P], host).  condense: as process_dev's."""
         from . import _capi as capi
         from .ingest import LegacyIngest
         if self._ingest is None:
@@ -129,7 +161,8 @@ class DmxFrameProcessor:
         runs, a = [], 0
         for b in range(1, F + 1):
             if b == F or bpn[b] != bpn[a]:
-                out = self.process_dev(echo[a:b], int(bpn[a]), with_flagV=with_flagV, max_hits=max_hits)
+                out = self.process_dev(echo[a:b], int(bpn[a]), with_flagV=with_flagV, max_hits=max_hits,
+                                       condense=condense)
                 out.update(frames=(a, b), beamPosNum=int(bpn[a]), frameInd=frame_ind[a:b], angleCode=code[a:b])
                 runs.append(out)
                 a = b
