@@ -604,6 +604,89 @@ int rsp_condense_dev(rsp_ctx* ctx, const float* d_amp, const uint8_t* d_flag, in
                      int64_t batch, const rsp_condense_params* cp, uint8_t* d_peak,
                      int32_t max_plots, int32_t* d_plots /* nullable */, int32_t* d_count, void* stream);
 
+/* ---- clutter map: detection in the zero-velocity band the chain blanks -------------------- */
+/* fun_0v_pressing writes zeros over the Doppler rows round zero velocity, executeCFAR strips
+ * rows 1..M0+1 and V-M0+1..V, and the DMX main zeroes rows 1:MTD_0_num+1 and
+ * end-MTD_0_num+1:end: inside that band the chain flags nothing, a hovering target included.
+ * rsp_cmap_dev is the classical MTD's answer: for each cell of the band's Doppler filters it
+ * keeps a recursive average over CPIs (the "map") and flags a cell that stands over its own
+ * history.  It is the one stage that carries state from call to call; the state (d_map, d_age)
+ * is the caller's memory.
+ *
+ * Input: the pulse-compressed rows, d_pc complex64 [batch][beams][P][ld] (rsp_pc_dev's output).
+ * Band amplitude of signed DFT bin q_k = q_lo + k, k < K = q_hi - q_lo + 1:
+ *   a[b][k][r] = sum over beams of | sum_p win[p] * pc[p][r] * exp(-2 pi j q_k p / V) |
+ * which is the value the MTD writes to the RDM row of bin q_k (row q_k mod V, or
+ * (q_k + V/2) mod V of an fftshifted RDM) before that row is zeroed.  The table
+ * win[p] * exp(...) is built in fp64 on the host, stored as fp32 and cached in the context by
+ * (P, V, window, window_beta, q_lo, q_hi): the first call with a new key allocates and uploads
+ * it synchronously, later calls only launch.  The sum over the pulses is an fp32 fmaf chain in
+ * pulse order, or with a pulse split (rsp_cmap_plan_t.split = 4) four such chains over quarters
+ * of the pulses added in quarter order.
+ *
+ * Map: the CPIs of a batch are consecutive in time and are applied in batch order, also when
+ * several share a slot.  With s = d_slot[b] (0 when d_slot is NULL), m = map[s][k][r],
+ * n = age[s], every operation a separate fp32 operation (nothing is contracted):
+ *   flag = n >= max(warmup, 1) && a >= (float)T * m
+ *   m'   = a                       when n == 0
+ *   m'   = m                       when hold && flag
+ *   m'   = m + (float)w * (a - m)  otherwise
+ * and after the CPI's cells age[s] = n + 1, saturating at INT32_MAX.  A CPI whose slot is
+ * negative (or >= slots) writes its band amplitudes and zero flags and touches no state.
+ * Reset = zeroing d_age (the map needs no clearing: n == 0 overwrites it).
+ * The fp32 map follows the exact recursion to about 2^-24 / w relative (each update rounds m
+ * once and the recursion forgets an error at the rate w), so its error grows as 1 / w:
+ * 2.4e-7 at w = 1/4, 4.8e-7 at w = 1/8, 6e-6 at w = 1/100.
+ * No atomics and no floating-point combination whose order depends on scheduling: two runs give
+ * the same bytes, and a sequence of CPIs gives the same map, age, band and flags in one batch as
+ * in any split into consecutive calls.
+ *
+ * d_map float32 [slots][K][R], d_age int32 [slots], d_band float32 [batch][K][R] or NULL (the
+ * amplitudes then pass through the context's grow-only pool, batch*K*R*4 bytes), d_flag uint8
+ * [batch][K][R].  None may overlap another or d_pc.  Arguments are checked before the context
+ * is looked at (RSP_ERR_ARG with a message).  Asynchronous on `stream`; works on any context,
+ * the CFAR-only kind included. */
+#define RSP_CMAP_MAX_BINS 64
+typedef struct {
+    int64_t P, V;            /* pulses; DFT length V >= P (zero-padded), V = 0 means P.  ANY P >= 2: a direct DFT has no radix limit */
+    int32_t beams;           /* 1, or 2: amplitude = |X_L| + |X_R| as the DMX sum plane */
+    int32_t window;          /* rsp_window */
+    double  window_beta;
+    int32_t q_lo, q_hi;      /* signed DFT bins q_lo..q_hi (q_lo <= 0 <= q_hi not required), K = q_hi-q_lo+1 <= 64, |q| < V/2 */
+    int32_t warmup;          /* a slot flags nothing before it has absorbed max(warmup, 1) CPIs */
+    int32_t hold;            /* 1: a flagged cell does not update its map value */
+    double  T;               /* threshold factor */
+    double  w;               /* 0 < w <= 1 */
+    int64_t ld, cpi_stride;  /* row pitch (0 = R) and elements between CPIs (0 = beams*P*ld) of d_pc; overlapping CPIs allowed (window mode) */
+} rsp_cmap_params;
+
+int rsp_cmap_dev(rsp_ctx* ctx, const void* d_pc /* complex64 [batch][beams][P][ld] */, int64_t R, int64_t batch,
+                 const rsp_cmap_params* mp, const int32_t* d_slot /* [batch]; NULL = slot 0; < 0: CPI updates nothing */,
+                 int32_t slots, float* d_map /* [slots][K][R] */, int32_t* d_age /* [slots] */,
+                 float* d_band /* [batch][K][R], nullable */, uint8_t* d_flag /* [batch][K][R] */, void* stream);
+
+/* The band kernel instance a call takes (read-only; nothing is launched).  The K bins run in
+ * `passes` groups of `bins_per_pass` (compile-time; bin k is accumulator k % bins_per_pass of pass
+ * k / bins_per_pass, the table is padded with zero entries to kpad = passes * bins_per_pass).
+ * vec: adjacent range columns per thread, 2 = 16-byte loads (R, ld and cpi_stride even), 1 =
+ * 8-byte loads; a call whose d_pc is not 16-byte or d_band not 8-byte aligned takes vec = 1
+ * whatever the plan says (same bytes out: a column's arithmetic does not depend on vec).
+ * split: waves of a workgroup that share a column's pulses, 4 where R <= 1024 and P >= 256 (the
+ * columns alone would not fill the part), else 1; it depends on R and P only, never on batch, so
+ * a split of the batch cannot change a bit.  ctx may be NULL. */
+typedef struct {
+    int32_t K, kpad;
+    int32_t bins_per_pass;   /* 4 (K <= 4) or 16 */
+    int32_t passes;
+    int32_t vec;             /* 1 or 2 */
+    int32_t split;           /* 1 or 4 */
+    int32_t threads;         /* per band workgroup: 64 * split */
+    int32_t reserved;
+    int64_t table_bytes;     /* the cached table: P * kpad * 8 */
+    int64_t pool_bytes;      /* the context pool used when d_band == NULL: batch * K * R * 4 */
+} rsp_cmap_plan_t;
+int rsp_cmap_plan(rsp_ctx* ctx, int64_t R, int64_t batch, const rsp_cmap_params* mp, rsp_cmap_plan_t* out);
+
 /* ---- detection scoring against truth (main_cfar.m's evaluation functions) ---------------- */
 /* The four local functions at the end of MatlabProcess_xuzerui/CFAR_WangCai/main_cfar.m, the
  * reason for its `for T=[5]` threshold loop (:40), over a device-resident batch of flag matrices:

@@ -221,7 +221,7 @@ int rsp_destroy(rsp_ctx* ctx) {
     for (void* p : ctx->owned) hipFree(p);
     DevBuf* bufs[] = {&ctx->pf_gain, &ctx->scratch_pc, &ctx->cat_tmp, &ctx->tmp_flagV, &ctx->tmp_rdm, &ctx->hit_list, &ctx->hit_ctr,
                       &ctx->st_in, &ctx->st_canon, &ctx->st_rdm, &ctx->st_flag, &ctx->st_flagV, &ctx->st_t,
-                      &ctx->meas_band, &ctx->ing_meta, &ctx->scr_ps, &ctx->cond_tmp};
+                      &ctx->meas_band, &ctx->ing_meta, &ctx->scr_ps, &ctx->cond_tmp, &ctx->cmap_band};
     for (DevBuf* b : bufs)
         if (b->p) hipFree(b->p);
     for (auto& e : ctx->evs) {
@@ -1610,6 +1610,139 @@ int rsp_condense_dev(rsp_ctx* ctx, const float* d_amp, const uint8_t* d_flag, in
                                           ctx->cond_tmp.p, (hipStream_t)stream));
     }
     return scratch_release(ctx, (hipStream_t)stream);
+}
+
+// ------------------------------------------------------------------ clutter map
+// Everything the host can check without a context; fills the resolved shape and the plan.
+static int cmap_check(rsp_ctx* ctx, const char* who, int64_t R, int64_t batch, const rsp_cmap_params* mp, rsp::CmapArgs* a,
+                      int64_t* Vout) {
+    if (!mp) return fail(ctx, RSP_ERR_ARG, "%s: null argument", who);
+    const int64_t P = mp->P, V = mp->V ? mp->V : mp->P;
+    if (P < 2 || P > ((int64_t)1 << 24) || V < P || V > ((int64_t)1 << 30))
+        return fail(ctx, RSP_ERR_ARG, "%s: bad P = %lld / V = %lld (2 <= P <= V)", who, (long long)P, (long long)V);
+    if (R < 1 || R > 0x7fffffff || batch < 0 || batch > 0x7fffffff)
+        return fail(ctx, RSP_ERR_ARG, "%s: bad shape R = %lld, batch = %lld", who, (long long)R, (long long)batch);
+    if (mp->beams != 1 && mp->beams != 2) return fail(ctx, RSP_ERR_ARG, "%s: beams = %d (1 or 2)", who, mp->beams);
+    if (mp->window != RSP_WIN_KAISER && mp->window != RSP_WIN_HAMMING && mp->window != RSP_WIN_RECT)
+        return fail(ctx, RSP_ERR_ARG, "%s: unknown window %d", who, mp->window);
+    if (mp->window == RSP_WIN_KAISER && !(mp->window_beta >= 0.0 && mp->window_beta < 700.0))
+        return fail(ctx, RSP_ERR_ARG, "%s: window_beta %g", who, mp->window_beta);
+    const int64_t K = (int64_t)mp->q_hi - (int64_t)mp->q_lo + 1;
+    if (K < 1 || K > RSP_CMAP_MAX_BINS)
+        return fail(ctx, RSP_ERR_ARG, "%s: K = %lld bins (q %d..%d) outside 1..%d", who, (long long)K, mp->q_lo,
+                    mp->q_hi, RSP_CMAP_MAX_BINS);
+    const int64_t qa = std::llabs((long long)mp->q_lo), qb = std::llabs((long long)mp->q_hi);
+    if (2 * (qa > qb ? qa : qb) >= V)
+        return fail(ctx, RSP_ERR_ARG, "%s: bins %d..%d need |q| < V/2 (V = %lld)", who, mp->q_lo, mp->q_hi,
+                    (long long)V);
+    if (mp->warmup < 0 || (mp->hold != 0 && mp->hold != 1))
+        return fail(ctx, RSP_ERR_ARG, "%s: warmup %d / hold %d", who, mp->warmup, mp->hold);
+    if (!(mp->T > 0.0) || !std::isfinite(mp->T)) return fail(ctx, RSP_ERR_ARG, "%s: threshold T = %g", who, mp->T);
+    if (!(mp->w > 0.0 && mp->w <= 1.0)) return fail(ctx, RSP_ERR_ARG, "%s: w = %g outside (0, 1]", who, mp->w);
+    const int64_t ld = mp->ld ? mp->ld : R;
+    if (ld < R || ld > ((int64_t)1 << 40))
+        return fail(ctx, RSP_ERR_ARG, "%s: row pitch %lld too small for %lld columns", who, (long long)ld, (long long)R);
+    const int64_t cs = mp->cpi_stride ? mp->cpi_stride : mp->beams * P * ld;
+    if (cs < 1) return fail(ctx, RSP_ERR_ARG, "%s: CPI stride %lld", who, (long long)cs);
+    a->P = (int)P;
+    a->R = (int)R;
+    a->K = (int)K;
+    a->beams = mp->beams;
+    a->warmup = mp->warmup;
+    a->hold = mp->hold;
+    a->T = (float)mp->T;
+    a->w = (float)mp->w;
+    a->ld = ld;
+    a->cs = cs;
+    int passes = 0;
+    rsp::cmap_plan(P, R, K, ld, cs, &a->kb, &passes, &a->vec, &a->split);
+    a->kpad = passes * a->kb;
+    *Vout = V;
+    return RSP_OK;
+}
+
+int rsp_cmap_plan(rsp_ctx* ctx, int64_t R, int64_t batch, const rsp_cmap_params* mp, rsp_cmap_plan_t* out) {
+    if (!out) return fail(ctx, RSP_ERR_ARG, "rsp_cmap_plan: null argument");
+    rsp::CmapArgs a{};
+    int64_t V = 0;
+    int rc = cmap_check(ctx, "rsp_cmap_plan", R, batch, mp, &a, &V);
+    if (rc) return rc;
+    memset(out, 0, sizeof(*out));
+    out->K = a.K;
+    out->kpad = a.kpad;
+    out->bins_per_pass = a.kb;
+    out->passes = a.kpad / a.kb;
+    out->vec = a.vec;
+    out->split = a.split;
+    out->threads = 64 * a.split;
+    out->table_bytes = (int64_t)a.P * a.kpad * 8;
+    out->pool_bytes = batch * a.K * R * 4;
+    return RSP_OK;
+}
+
+// tab[p][k] = win[p] * exp(-2 pi j (q_lo + k) p / V) for k < K, zero for the padding, fp64 -> fp32
+static int cmap_table(rsp_ctx* ctx, const rsp_cmap_params* mp, const rsp::CmapArgs& a, int64_t V, const float2** out) {
+    int64_t beta_bits = 0;
+    if (mp->window == RSP_WIN_KAISER) memcpy(&beta_bits, &mp->window_beta, sizeof(beta_bits));
+    const std::vector<int64_t> key{a.P, V, mp->window, beta_bits, mp->q_lo, mp->q_hi, a.kpad};
+    auto it = ctx->cmap_tab.find(key);
+    if (it != ctx->cmap_tab.end()) {
+        *out = it->second;
+        return RSP_OK;
+    }
+    const std::vector<double> win = make_window(mp->window, mp->window_beta, a.P);
+    std::vector<float2> h((size_t)a.P * a.kpad, make_float2(0.0f, 0.0f));
+    for (int64_t p = 0; p < a.P; ++p)
+        for (int k = 0; k < a.K; ++k) {
+            int64_t e = ((int64_t)(mp->q_lo + k) * p) % V;   // the angle's index, reduced in integers
+            if (e < 0) e += V;
+            const double ang = -2.0 * M_PI * (double)e / (double)V;
+            h[(size_t)p * a.kpad + k] = make_float2((float)(win[p] * std::cos(ang)), (float)(win[p] * std::sin(ang)));
+        }
+    float2* d = nullptr;
+    int rc = upload(ctx, h, &d);
+    if (rc) return rc;
+    ctx->cmap_tab[key] = d;
+    *out = d;
+    return RSP_OK;
+}
+
+int rsp_cmap_dev(rsp_ctx* ctx, const void* d_pc, int64_t R, int64_t batch, const rsp_cmap_params* mp,
+                 const int32_t* d_slot, int32_t slots, float* d_map, int32_t* d_age, float* d_band, uint8_t* d_flag,
+                 void* stream) {
+    // everything that can be checked on the host comes before the context is looked at
+    if (!mp || !d_pc || !d_map || !d_age || !d_flag) return fail(ctx, RSP_ERR_ARG, "rsp_cmap_dev: null argument");
+    rsp::CmapArgs a{};
+    int64_t V = 0;
+    int rc = cmap_check(ctx, "rsp_cmap_dev", R, batch, mp, &a, &V);
+    if (rc) return rc;
+    if (slots < 1 || slots > 65535) return fail(ctx, RSP_ERR_ARG, "rsp_cmap_dev: slots = %d outside 1..65535", slots);
+    a.slots = slots;
+    if ((int64_t)a.K * R > ((int64_t)1 << 36))
+        return fail(ctx, RSP_ERR_UNSUPPORTED, "rsp_cmap_dev: %d x %lld map cells per slot", a.K, (long long)R);
+    if (!ctx) return fail(nullptr, RSP_ERR_ARG, "rsp_cmap_dev: null ctx");
+    if (batch == 0) return RSP_OK;
+    if (!set_device(ctx)) return fail(ctx, RSP_ERR_HIP, "hipSetDevice failed");
+    const float2* tab = nullptr;
+    if ((rc = cmap_table(ctx, mp, a, V, &tab))) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    float* band = d_band;
+    if (!band) {
+        if ((rc = scratch_acquire(ctx, st))) return rc;
+        if ((rc = ensure(ctx, ctx->cmap_band, (size_t)batch * a.K * (size_t)R * 4)) != RSP_OK) return rc;
+        band = (float*)ctx->cmap_band.p;
+    }
+    const float2* pc = (const float2*)d_pc;
+    const int64_t cells = (int64_t)a.K * R;
+    for (int64_t b0 = 0; b0 < batch; b0 += 65535) {   // gridDim.z; the bytes do not depend on the cut
+        const int nb = (int)(batch - b0 < 65535 ? batch - b0 : 65535);
+        // the vector width is chosen once for the call: every launch sees the same alignment
+        rsp::CmapArgs ab = a;
+        if (((uintptr_t)pc & 15) || ((uintptr_t)band & 7)) ab.vec = 1;
+        HIP_TRY(ctx, rsp::launch_cmap_band(pc + b0 * a.cs, tab, ab, nb, band + b0 * cells, st));
+    }
+    HIP_TRY(ctx, rsp::launch_cmap_update(band, d_slot, a, batch, d_map, d_age, d_flag, st));
+    return d_band ? RSP_OK : scratch_release(ctx, st);
 }
 
 // ------------------------------------------------------------------ detection scoring

@@ -70,6 +70,9 @@ struct rsp_ctx {
     DevBuf meas_band;                   // measurement: per-(CPI, band, column) hit counts
     DevBuf scr_ps;                      // injection: per-CPI sums, ratios and pulse phases (InjectArgs::ps)
     DevBuf cond_tmp;                    // condensation: labels, keys and hit lists of one chunk of CPIs
+    DevBuf cmap_band;                   // clutter map: the band amplitudes of a call without d_band
+    // clutter map: window x DFT tables [P][kpad] by {P, V, window, beta bits, q_lo, q_hi, kpad} (in `owned`)
+    std::map<std::vector<int64_t>, float2*> cmap_tab;
     DevBuf ing_meta;                    // ingest: per-PRT record offsets and types
     DevBuf st_in, st_canon, st_rdm, st_flag, st_flagV, st_t;  // host-API staging (rsp_cfar)
     // Pipelined host-buffer path (rsp_pc_mtd_cfar / rsp_pc_mtd): chunk k's H2D (copy stream),

@@ -189,6 +189,24 @@ size_t condense_scratch_per_cpi(int64_t V, int64_t R, int32_t max_plots);
 hipError_t launch_condense(const float* amp, const uint8_t* flag, uint8_t* peak, int batch, CondenseArgs a,
                            int32_t* plots, int32_t* count, void* scratch, hipStream_t st);
 
+// Clutter map (rsp_cmap.hip): rsp_cmap_params with the shape, the resolved pitches and the plan.
+struct CmapArgs {
+    int P, R, K, kpad;
+    int beams;
+    int kb, vec, split;   // the band kernel instance (rsp_cmap_plan_t)
+    int warmup, hold, slots;
+    float T, w;
+    int64_t ld, cs;       // row pitch and CPI stride of the PC rows, in complex elements
+};
+// The instance a shape takes; vec from the shape alone (launch_cmap_band also looks at the pointers).
+void cmap_plan(int64_t P, int64_t R, int64_t K, int64_t ld, int64_t cs, int* kb, int* passes, int* vec, int* split);
+// band[b][k][r] for b < batch (at most 65535); tab: float2 [P][kpad].
+hipError_t launch_cmap_band(const float2* pc, const float2* tab, const CmapArgs& a, int batch, float* band,
+                            hipStream_t st);
+// The recursion over the batch's CPIs in order, then the ages.
+hipError_t launch_cmap_update(const float* band, const int32_t* slot, const CmapArgs& a, int64_t batch, float* map,
+                              int32_t* age, uint8_t* flag, hipStream_t st);
+
 // Detection scoring (rsp_score.hip): rsp_score_params with the shape and the resolved pitches.
 struct ScoreArgs {
     int V, R;

@@ -5,10 +5,12 @@ include/rsp.h); this package is the Python mirror of the reference's MATLAB inte
 (rsp.matlab), parameter presets (rsp.presets), the Engine wrapper (rsp.engine), the
 deterministic synthetic-echo generator (rsp.synth) and, behind the chain, the per-hit
 measurement (rsp.measure), the scoring of detections against truth (rsp.score) and, in
-front of it, the injection of simulated targets at a set SCR (rsp.inject).
+front of it, the injection of simulated targets at a set SCR (rsp.inject).  Beside the chain,
+rsp.cmap detects in the zero-velocity band the chain blanks, against a clutter map.
 """
-from . import _capi, presets, synth  # noqa: F401
+from . import _capi, cmap, presets, synth  # noqa: F401
 from ._capi import RspError, load_library  # noqa: F401
+from .cmap import ClutterMap, band_of  # noqa: F401
 from .engine import Engine, engine_for  # noqa: F401
 
 __version__ = "0.3.0"
