@@ -1,4 +1,5 @@
-// rsp_ctx.h -- the context behind the C ABI (private): what rsp_capi.cpp and rsp_host.cpp share.
+// rsp_ctx.h -- the context behind the C ABI (private): what rsp_capi.cpp, rsp_stages.cpp and
+// rsp_host.cpp share.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -118,6 +119,13 @@ struct rsp_ctx {
 int fail(rsp_ctx* ctx, int code, const char* fmt, ...);
 int ensure(rsp_ctx* ctx, DevBuf& b, size_t bytes);
 bool set_device(rsp_ctx* ctx);
+namespace rsp {
+// Order this call's use of the context scratch after the previous call's (on any stream).
+int scratch_acquire(rsp_ctx* ctx, hipStream_t s);
+int scratch_release(rsp_ctx* ctx, hipStream_t s);
+// Window of n points (RSP_WIN_*) in fp64.
+std::vector<double> make_window(int kind, double beta, int64_t n);
+}  // namespace rsp
 
 #define HIP_TRY(ctx, expr)                                                                   \
     do {                                                                                     \
@@ -126,3 +134,16 @@ bool set_device(rsp_ctx* ctx);
             return fail((ctx), RSP_ERR_HIP, "%s: %s (%s:%d)", #expr, hipGetErrorString(e_),   \
                         __FILE__, __LINE__);                                                 \
     } while (0)
+
+namespace rsp {
+// A host table into device memory the context owns (freed at destroy).
+template <typename T>
+int upload(rsp_ctx* ctx, const std::vector<T>& h, T** out) {
+    void* d = nullptr;
+    HIP_TRY(ctx, hipMalloc(&d, h.size() * sizeof(T)));
+    ctx->owned.push_back(d);
+    HIP_TRY(ctx, hipMemcpy(d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
+    *out = (T*)d;
+    return RSP_OK;
+}
+}  // namespace rsp

@@ -1,4 +1,4 @@
-// rsp_diag.h -- dev-only diagnostic switches of the PC / MTD kernels (rsp_kernels.hip), kept out
+// rsp_diag.h -- dev-only diagnostic switches of the PC / MTD kernels (rsp_pc.hip, rsp_mtd.hip), kept out
 // of the product source.  Every switch defaults to the product build; tools/build_variant.sh
 // builds a variant library with -D flags, and the A/B tools (tools/diag_pc.sh, tools/ab2.sh,
 // tools/diag_stamps.py) measure it.  None of these is reachable from include/rsp.h.
@@ -23,16 +23,25 @@ namespace rsp {
 // first waits for the wave's own memory operations, so "loads arrived" / "stores done" are
 // points in time.  Slots 8 and 9 hold the 100 MHz real-time clock at entry and exit; 10-12
 // split the FIR (staged, computed, stored).
+// Each unit that includes this header has its own array (internal linkage): kernel k = 0 is the
+// PC unit's, k = 1 the MTD unit's, and the rsp_diag_stamps export (rsp_pc.hip) fetches either.
 constexpr int kDiagSlots = 16, kDiagWG = 1 << 15;
-__device__ uint64_t g_diag[2][kDiagWG * kDiagSlots];
-__device__ __forceinline__ void diag_stamp(int k, int slot, bool wait, bool realtime = false) {
+static __device__ uint64_t g_diag[kDiagWG * kDiagSlots];
+__device__ __forceinline__ void diag_stamp(int slot, bool wait, bool realtime = false) {
     if (wait) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     const uint64_t t = realtime ? __builtin_amdgcn_s_memrealtime() : __builtin_amdgcn_s_memtime();
     const uint32_t wg = blockIdx.x + blockIdx.y * gridDim.x;
-    if (threadIdx.x == 0 && wg < (uint32_t)kDiagWG) g_diag[k][wg * kDiagSlots + slot] = t;
+    if (threadIdx.x == 0 && wg < (uint32_t)kDiagWG) g_diag[wg * kDiagSlots + slot] = t;
 }
-#define RSP_STAMP(k, slot, wait) diag_stamp(k, slot, wait)
-#define RSP_STAMP_RT(k, slot) diag_stamp(k, slot, false, true)
+// this unit's first n stamps to host (rsp_diag_stamps' return codes)
+static int diag_fetch(uint64_t* host, int64_t n) {
+    if (n < 0 || n > (int64_t)kDiagWG * kDiagSlots) return -1;
+    if (hipDeviceSynchronize() != hipSuccess) return -2;
+    return hipMemcpyFromSymbol(host, HIP_SYMBOL(g_diag), (size_t)n * 8, 0, hipMemcpyDeviceToHost) == hipSuccess ? 0 : -3;
+}
+int diag_fetch_mtd(uint64_t* host, int64_t n);   // rsp_mtd.hip
+#define RSP_STAMP(k, slot, wait) diag_stamp(slot, wait)
+#define RSP_STAMP_RT(k, slot) diag_stamp(slot, false, true)
 #else
 #define RSP_STAMP(k, slot, wait) ((void)0)
 #define RSP_STAMP_RT(k, slot) ((void)0)

@@ -517,8 +517,8 @@ static int host_chain(rsp_ctx* ctx, const void* echo, int32_t dtype, int32_t lay
         const void* d_echo = h.in[sl].p;
         int32_t d_dtype = ddtype;
         if (conv) {
-            HIP_TRY(ctx, rsp::launch_ingest(h.in[sl].p, ddtype, layout, (float2*)h.canon[sl].p, n * beams, (int)P,
-                                            (int)R, ctx->stream));
+            HIP_TRY(ctx, rsp::launch_canon(h.in[sl].p, ddtype, layout, (float2*)h.canon[sl].p, n * beams, (int)P,
+                                           (int)R, ctx->stream));
             d_echo = h.canon[sl].p;
             d_dtype = RSP_C64;
         }

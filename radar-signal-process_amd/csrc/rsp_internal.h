@@ -1,5 +1,6 @@
-// rsp_internal.h -- argument blocks shared by the C-ABI host code (rsp_capi.cpp) and the
-// HIP kernels (rsp_kernels.hip).  Not part of the public ABI.
+// rsp_internal.h -- argument blocks and launchers shared by the C-ABI host code (rsp_capi.cpp,
+// rsp_stages.cpp, rsp_host.cpp) and the HIP kernels (one rsp_<stage>.hip per stage).  Not part
+// of the public ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -33,6 +34,12 @@ inline hipError_t launch_once(LaunchOnce& L, int* value, F&& init) {
     std::call_once(L.once[dev], [&] { L.err[dev] = init(dev, &L.value[dev]); });
     if (value) *value = L.value[dev];
     return L.err[dev];
+}
+// Dynamic-LDS attribute of a kernel (once per device).
+inline hipError_t lds_attr(LaunchOnce& once, const void* kernel, size_t lds) {
+    return launch_once(once, nullptr, [&](int, int*) {
+        return hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    });
 }
 
 // One pulse-compression segment as the kernel sees it (see rsp_pc_segment).
@@ -389,8 +396,8 @@ hipError_t launch_cfar_r(const float* rdm, const uint8_t* flagV, uint8_t* flag, 
 // row in LDS: 10 bytes per cell)
 bool cfar_r_supported(const CfarRArgs& a);
 // dtype/layout conversion of a host-API input into [batch][P][R] complex float32.
-hipError_t launch_ingest(const void* in, int dtype, int layout, float2* out, int64_t batch,
-                         int P, int R, hipStream_t s);
+hipError_t launch_canon(const void* in, int dtype, int layout, float2* out, int64_t batch,
+                        int P, int R, hipStream_t s);
 // [batch][A][B] -> [batch][B][A] for 4-byte and 1-byte elements.
 hipError_t launch_transpose_f32(const float* in, float* out, int64_t batch, int A, int B,
                                 hipStream_t s);

@@ -2,7 +2,7 @@
 sweep (tests/test_gpu_mtd_instances.py).  No GPU code and no torch: tests/test_mtd_ref_cpu.py
 holds all of it to the oracle without a GPU.
 
-The MTD of one CPI, as the kernels' comments define it (rsp_kernels.hip, mtd_tile):
+The MTD of one CPI, as the kernels' comments define it (rsp_mtd.hip, mtd_tile):
 
   pulse p           pc[p] * w[p]
   with an MTI lag   (pc[p + lag] - pc[p]) * w[p], zero from pin - lag on

@@ -1,5 +1,5 @@
 """Build-time invariant of the shipped kernels (CPU only): the MTD tile's hand-counted LDS-DMA
-wait (`s_waitcnt vmcnt(Hook::kLoads)` in rsp_kernels.hip mtd_tile) covers exactly the DMA
+wait (`s_waitcnt vmcnt(Hook::kLoads)` in rsp_mtd.hip mtd_tile) covers exactly the DMA
 pieces -- kLoads range-job gathers issue between the last piece and the wait, none above the
 DMA -- in every mtd_kernel instance of lib/librsp.so (tools/isa_check.py)."""
 import os

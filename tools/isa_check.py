@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Build-time check of the MTD kernel's hand-counted LDS-DMA wait.
 
-mtd_tile (radar-signal-process_amd/csrc/rsp_kernels.hip, the kMtdDma path) issues the tile's
+mtd_tile (radar-signal-process_amd/csrc/rsp_mtd.hip, the kMtdDma path) issues the tile's
 `buffer_load_dwordx4 ... lds` pieces, then the range job's Hook::kLoads gathers, then an asm
 `s_waitcnt vmcnt(Hook::kLoads)` and an `s_barrier`, after which every wave reads the tile from
 LDS.  vmcnt counts vector-memory operations in issue order, so the asm wait covers the DMA
@@ -38,8 +38,9 @@ def _tool(name):
     return p if os.path.exists(p) else name
 
 
-def disassemble(lib=LIB):
-    """gfx950 disassembly of every device code object in the library's .hip_fatbin."""
+def disassemble(lib=LIB, tool_args=("llvm-objdump", "-d", "--mcpu=gfx950")):
+    """gfx950 disassembly of every device code object in the library's .hip_fatbin (or what
+    another LLVM tool, e.g. llvm-readelf --notes, prints for each of them)."""
     with tempfile.TemporaryDirectory() as d:
         fb = os.path.join(d, "fb.bin")
         subprocess.check_call([_tool("llvm-objcopy"), "--dump-section", ".hip_fatbin=" + fb, lib, os.path.join(d, "x")])
@@ -54,7 +55,7 @@ def disassemble(lib=LIB):
                                 "--output=" + co, "--unbundle"], capture_output=True)
             if r.returncode != 0 or not os.path.exists(co) or os.path.getsize(co) == 0:
                 continue
-            text.append(subprocess.run([_tool("llvm-objdump"), "-d", "--mcpu=gfx950", co], capture_output=True,
+            text.append(subprocess.run([_tool(tool_args[0]), *tool_args[1:], co], capture_output=True,
                                        text=True, check=True).stdout)
         return "\n".join(text)
 
