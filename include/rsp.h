@@ -687,6 +687,54 @@ typedef struct {
 } rsp_cmap_plan_t;
 int rsp_cmap_plan(rsp_ctx* ctx, int64_t R, int64_t batch, const rsp_cmap_params* mp, rsp_cmap_plan_t* out);
 
+/* ---- Doppler line width per range column (ampConstrWidthEst.m) ---------------------------- */
+/* widthDots = ampConstrWidthEst(specData, ampConstr, interpFlag, interpTimes) of
+ * MatlabProcess_xuzerui/CFAR_WangCai, for every column of an amplitude plane that carries a hit:
+ *   y = abs(fftshift(specData))                                  (the rotation by floor(V/2) when shift = 1)
+ *   s = interp1(0:V-1, y, 0:1/interpTimes:V-1, 'spline')         (not-a-knot cubic, unit knots; s = y at interp = 1)
+ *   M1 = max(s); the samples with 20*log10(s/M1) >= ampConstr; the last one's abscissa minus the first's.
+ * A negative s/M1 makes MATLAB's log10 complex and >= compares real parts, so the test is
+ * |s_i| >= 10^(amp_constr/20) * M1, which is how it is evaluated here (the level in fp64 on the
+ * host, no logarithm on the device).  The figures (70, 71) and the commented-out walk outward from
+ * the peak (:22-35) are not part of it.
+ *
+ * d_amp float32 and d_flag uint8 are [batch][V][ld] windows of R columns with the geometry of
+ * rsp_motion_measure_dev and rsp_condense_dev.  A column is computed when any of its V flag bytes
+ * inside the window is nonzero (d_flag == NULL: every column); the amplitudes of a column without
+ * a hit are not read.  d_span int32 [batch][R][2]: a computed column's {first, last}, the 0-based
+ * indices on the 1/interp grid (sample i lies at abscissa i / interp, i <= (V-1)*interp) of its
+ * first and last sample at or above the level, so widthDots = (last - first) / interp; {-1, -1}
+ * for a column that is not computed or whose M1 is not positive (an all-zero column: the
+ * reference's 0/0 and empty set, width 0).  Every entry is written.  d_count int32 [batch]: the
+ * columns computed.  Amplitudes are magnitudes; a NaN or Inf in a computed column leaves that
+ * column's span unspecified.
+ *
+ * From the float32 inputs on the arithmetic is fp64: the second derivatives solve the (1, 4, 1)
+ * rows by the Thomas algorithm (its two sweeps as parallel scans of affine maps)
+ * and each interval is evaluated in the local power form.  The operation order differs from
+ * MATLAB's, so a sample within rounding (a small multiple of 1e-16 of M1) of the level may fall
+ * on the other side; away from such ties the integers are the reference's.  amp_constr = 0 is
+ * refused: the level would coincide with the maximum itself, a tie in every column.
+ * No floating-point operation depends on scheduling (the count is an integer sum): two runs give
+ * the same bytes, and a CPI alone gives the bytes it gives inside a batch.
+ * Limits: 4 <= V <= 2048, R >= 1, ld >= R.  Arguments are checked before the context is looked at
+ * (RSP_ERR_ARG with a message).  Asynchronous on `stream`; works on any context, the CFAR-only
+ * kind included; uses no context scratch. */
+#define RSP_WIDTH_MIN_V 4
+#define RSP_WIDTH_MAX_V 2048
+typedef struct {
+    double  amp_constr;   /* ampConstr [dB]: -200 <= amp_constr < 0 */
+    int32_t interp;       /* interpTimes 1..64; 1 = interpFlag 0 */
+    int32_t shift;        /* 1: fftshift each column first, as the .m does (the DMX planes, which carry no shift);
+                             0: the plane is already centred (the v2 / legacy RDM) */
+    int64_t ld;           /* row pitch in elements (0 = R), as rsp_measure_params.ld */
+    int64_t cpi_stride;   /* elements between CPIs (0 = V * ld) */
+} rsp_width_params;
+
+int rsp_spec_width_dev(rsp_ctx* ctx, const float* d_amp, const uint8_t* d_flag /* nullable */,
+                       int64_t V, int64_t R, int64_t batch, const rsp_width_params* wp,
+                       int32_t* d_span, int32_t* d_count, void* stream);
+
 /* ---- detection scoring against truth (main_cfar.m's evaluation functions) ---------------- */
 /* The four local functions at the end of MatlabProcess_xuzerui/CFAR_WangCai/main_cfar.m, the
  * reason for its `for T=[5]` threshold loop (:40), over a device-resident batch of flag matrices:

@@ -214,6 +214,23 @@ hipError_t launch_cmap_band(const float2* pc, const float2* tab, const CmapArgs&
 hipError_t launch_cmap_update(const float* band, const int32_t* slot, const CmapArgs& a, int64_t batch, float* map,
                               int32_t* age, uint8_t* flag, hipStream_t st);
 
+// Doppler line width (rsp_width.hip): rsp_width_params with the shape and the resolved pitches.
+struct WidthArgs {
+    int V, R;
+    int interp, shift;
+    int lg, pitch;    // (launch_width) log2 of a lane's chunk of rows; padded LDS elements per column
+    double level;     // 10^(amp_constr / 20)
+    int64_t ld, cs;   // row pitch and CPI stride of the amplitude / flag planes, in elements
+};
+// A lane's chunk of rows (1 << *lg, 64 chunks cover V) and the chunk-padded LDS elements of a column.
+void width_geometry(int V, int* lg, int* pitch);
+// Dynamic LDS of a width_kernel workgroup: four columns of V floats and, with interp > 1, V doubles,
+// chunk-padded.
+size_t width_lds_bytes(int V, int interp);
+// span [batch][R][2], count [batch] (batch at most 65535); flag may be null (every column).
+hipError_t launch_width(const float* amp, const uint8_t* flag, int batch, const WidthArgs& a, int32_t* span,
+                        int32_t* count, hipStream_t st);
+
 // Detection scoring (rsp_score.hip): rsp_score_params with the shape and the resolved pitches.
 struct ScoreArgs {
     int V, R;

@@ -1,5 +1,5 @@
 // rsp_stages.cpp -- the C ABI's stage entry points around the chain (include/rsp.h): post-detection
-// measurement, plot condensation, clutter map, detection scoring, echo pre-filters, target
+// measurement, plot condensation, clutter map, Doppler line width, detection scoring, echo pre-filters, target
 // injection, raw-data ingest and the legacy record ingest.  Each validates its arguments and
 // launches its stage's kernels (rsp_<stage>.hip); the context, the presets and the PC -> MTD ->
 // CFAR chain are in rsp_capi.cpp.
@@ -267,6 +267,47 @@ int rsp_cmap_dev(rsp_ctx* ctx, const void* d_pc, int64_t R, int64_t batch, const
     }
     HIP_TRY(ctx, rsp::launch_cmap_update(band, d_slot, a, batch, d_map, d_age, d_flag, st));
     return d_band ? RSP_OK : scratch_release(ctx, st);
+}
+
+// ------------------------------------------------------------------ Doppler line width
+int rsp_spec_width_dev(rsp_ctx* ctx, const float* d_amp, const uint8_t* d_flag, int64_t V, int64_t R, int64_t batch,
+                       const rsp_width_params* wp, int32_t* d_span, int32_t* d_count, void* stream) {
+    // everything that can be checked on the host comes before the context is looked at
+    if (!wp || !d_amp || !d_span || !d_count) return fail(ctx, RSP_ERR_ARG, "rsp_spec_width_dev: null argument");
+    if (!(wp->amp_constr >= -200.0 && wp->amp_constr < 0.0))
+        return fail(ctx, RSP_ERR_ARG, "rsp_spec_width_dev: amp_constr %g dB outside [-200, 0)", wp->amp_constr);
+    if (wp->interp < 1 || wp->interp > 64)
+        return fail(ctx, RSP_ERR_ARG, "rsp_spec_width_dev: interp %d outside 1..64", wp->interp);
+    if (wp->shift != 0 && wp->shift != 1) return fail(ctx, RSP_ERR_ARG, "rsp_spec_width_dev: shift %d", wp->shift);
+    if (V < RSP_WIDTH_MIN_V || V > RSP_WIDTH_MAX_V)
+        return fail(ctx, RSP_ERR_ARG, "rsp_spec_width_dev: V = %lld outside %d..%d", (long long)V, RSP_WIDTH_MIN_V,
+                    RSP_WIDTH_MAX_V);
+    if (R < 1 || R > (1 << 24) || batch < 0 || batch > 0x7fffffff)
+        return fail(ctx, RSP_ERR_ARG, "rsp_spec_width_dev: bad shape R = %lld, batch = %lld", (long long)R,
+                    (long long)batch);
+    if (wp->ld < 0 || wp->cpi_stride < 0)
+        return fail(ctx, RSP_ERR_ARG, "rsp_spec_width_dev: negative row pitch / CPI stride");
+    const int64_t ld = wp->ld ? wp->ld : R, cs = wp->cpi_stride ? wp->cpi_stride : V * ld;
+    if (ld < R || ld > ((int64_t)1 << 40) || cs < (V - 1) * ld + R)
+        return fail(ctx, RSP_ERR_ARG, "rsp_spec_width_dev: row pitch %lld / CPI stride %lld too small for %lld x %lld",
+                    (long long)ld, (long long)cs, (long long)V, (long long)R);
+    if (!ctx) return fail(nullptr, RSP_ERR_ARG, "rsp_spec_width_dev: null ctx");
+    if (batch == 0) return RSP_OK;
+    if (!set_device(ctx)) return fail(ctx, RSP_ERR_HIP, "hipSetDevice failed");
+    rsp::WidthArgs a{};
+    a.V = (int)V;
+    a.R = (int)R;
+    a.interp = wp->interp;
+    a.shift = wp->shift;
+    a.level = std::pow(10.0, wp->amp_constr / 20.0);
+    a.ld = ld;
+    a.cs = cs;
+    for (int64_t b0 = 0; b0 < batch; b0 += 65535) {   // gridDim.y; a column's bytes do not depend on the cut
+        const int nb = (int)(batch - b0 < 65535 ? batch - b0 : 65535);
+        HIP_TRY(ctx, rsp::launch_width(d_amp + b0 * cs, d_flag ? d_flag + b0 * cs : nullptr, nb, a, d_span + b0 * R * 2,
+                                       d_count + b0, (hipStream_t)stream));
+    }
+    return RSP_OK;
 }
 
 // ------------------------------------------------------------------ detection scoring

@@ -6,11 +6,13 @@ include/rsp.h); this package is the Python mirror of the reference's MATLAB inte
 deterministic synthetic-echo generator (rsp.synth) and, behind the chain, the per-hit
 measurement (rsp.measure), the scoring of detections against truth (rsp.score) and, in
 front of it, the injection of simulated targets at a set SCR (rsp.inject).  Beside the chain,
-rsp.cmap detects in the zero-velocity band the chain blanks, against a clutter map.
+rsp.cmap detects in the zero-velocity band the chain blanks, against a clutter map, and
+rsp.width measures how wide the Doppler line of a detection's range column stands.
 """
-from . import _capi, cmap, presets, synth  # noqa: F401
+from . import _capi, cmap, presets, synth, width  # noqa: F401
 from ._capi import RspError, load_library  # noqa: F401
 from .cmap import ClutterMap, band_of  # noqa: F401
+from .width import Width, ampConstrWidthEst, width_dots  # noqa: F401
 from .engine import Engine, engine_for  # noqa: F401
 
 __version__ = "0.3.0"

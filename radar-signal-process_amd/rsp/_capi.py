@@ -34,7 +34,7 @@ EXPORTS = ("rsp_version", "rsp_create", "rsp_destroy", "rsp_last_error", "rsp_se
            "rsp_pc_mtd_cfar_f64", "rsp_cfar_f64", "rsp_set_range_concat", "rsp_score_dev", "rsp_score_summary",
            "rsp_set_pc_prune", "rsp_set_lane_chunks", "rsp_pc_plan", "rsp_scr_dev", "rsp_inject_dev", "rsp_scr_gain",
            "rsp_cfar_plan", "rsp_legacy_record_bytes", "rsp_ingest_legacy_dev", "rsp_condense_dev", "rsp_cmap_dev",
-           "rsp_cmap_plan")
+           "rsp_cmap_plan", "rsp_spec_width_dev")
 RSP_NKERNELS = 4
 KERNEL_NAMES = ("pc_kernel", "mtd_kernel", "cfar_r_kernel", "cfar_v_kernel")
 
@@ -113,6 +113,14 @@ class rsp_cmap_plan_t(C.Structure):
     _fields_ = [("K", C.c_int32), ("kpad", C.c_int32), ("bins_per_pass", C.c_int32), ("passes", C.c_int32),
                 ("vec", C.c_int32), ("split", C.c_int32), ("threads", C.c_int32), ("reserved", C.c_int32),
                 ("table_bytes", C.c_int64), ("pool_bytes", C.c_int64)]
+
+
+RSP_WIDTH_MIN_V, RSP_WIDTH_MAX_V = 4, 2048
+
+
+class rsp_width_params(C.Structure):
+    _fields_ = [("amp_constr", C.c_double), ("interp", C.c_int32), ("shift", C.c_int32), ("ld", C.c_int64),
+                ("cpi_stride", C.c_int64)]
 
 
 class rsp_score_params(C.Structure):
@@ -255,6 +263,8 @@ def load_library(path=None):
     lib.rsp_cmap_dev.argtypes = [vp, vp, i64, i64, C.POINTER(rsp_cmap_params), vp, i32, vp, vp, vp, vp, vp]
     lib.rsp_cmap_plan.restype = C.c_int
     lib.rsp_cmap_plan.argtypes = [vp, i64, i64, C.POINTER(rsp_cmap_params), C.POINTER(rsp_cmap_plan_t)]
+    lib.rsp_spec_width_dev.restype = C.c_int
+    lib.rsp_spec_width_dev.argtypes = [vp, vp, vp, i64, i64, i64, C.POINTER(rsp_width_params), vp, vp, vp]
     lib.rsp_score_dev.restype = C.c_int
     lib.rsp_score_dev.argtypes = [vp, vp, vp, i64, i64, i64, C.POINTER(rsp_score_params), vp, vp, vp]
     lib.rsp_score_summary.restype = C.c_int

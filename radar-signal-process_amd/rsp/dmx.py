@@ -66,16 +66,19 @@ class DmxFrameProcessor:
         self.device = self.meas.device
         self._ingest = None
         self._cond = None
+        self._width = None
 
     def close(self):
         self.eng.close()
         self.meas.close()
         if self._cond is not None:
             self._cond.close()
+        if self._width is not None:
+            self._width.close()
         if self._ingest is not None:
             self._ingest.close()
 
-    def process_dev(self, echo, beamPosNum, with_flagV=True, max_hits=4096, condense=None):
+    def process_dev(self, echo, beamPosNum, with_flagV=True, max_hits=4096, condense=None, width=None):
         """echo: complex64 [batch][2][P][R] (left, right) on the device.  Returns a dict of
         device outputs: the planes (sum, diff, flag, flagV) and, per part ('short', 'long') and
         flag kind ('flag', 'flagV'), (est, cells, count) as Measure.measure_dev gives them.
@@ -86,8 +89,21 @@ class DmxFrameProcessor:
         out[(part, kind)] is the measurement of the peaks, out[(part, kind, 'plots')] =
         (plots, count) of the condensation (at most max_hits records per CPI), out['peak'] /
         out['peakV'] the peak planes.  wrap_v defaults to False: this layout has no fftshift, and
-        its seam lies in the zeroed zero-velocity band."""
+        its seam lies in the zeroed zero-velocity band.
+
+        width = dict(amp_constr=-6.0, interp=4): every (part, kind) that is measured also gets
+        out[(part, kind, 'width')] = (span, count) of Width.width_dev over the same column window
+        of the sum plane (shift = 1: these planes carry no fftshift), on the columns of the flag
+        plane that was measured (the peak plane when condensing), and out[(part, kind,
+        'widthDots')], float64 [batch][max_hits]: the width of each measured hit's column, gathered
+        through the measurement's cells, NaN past the count."""
         import torch
+        if width is not None:
+            width = dict(width)
+            wopt = (width.pop("amp_constr", -6.0), width.pop("interp", 4))
+            if width:
+                raise TypeError("process_dev: width takes amp_constr and interp, not %s" % sorted(width))
+            width = wopt
         B = echo.shape[0]
         shp = (B, self.spec.V, self.spec.R_out)
         dev = self.device
@@ -102,15 +118,33 @@ class DmxFrameProcessor:
                              o["beamAngleStep"], o["eleAngleComp"], o["eleAngleSysErr"], self.spec.radar["M0"])
         ps = self.spec.cfar_segments[0][1]
         if condense is not None:
-            return self._measure_plots(out, p, ps, with_flagV, max_hits, dict(condense))
+            return self._measure_plots(out, p, ps, with_flagV, max_hits, dict(condense), width)
         for fk in ("flag", "flagV") if with_flagV else ("flag",):
-            out[("short", fk)] = self.meas.measure_dev(out["sum"], out["diff"], out[fk], p, rS, vS,
-                                                       max_hits=max_hits, cols=(0, ps))
-            out[("long", fk)] = self.meas.measure_dev(out["sum"], out["diff"], out[fk], p, rL, vS,
-                                                      max_hits=max_hits, cols=(ps, self.spec.R_out))
+            for part, cols, rs in (("short", (0, ps), rS), ("long", (ps, self.spec.R_out), rL)):
+                out[(part, fk)] = self.meas.measure_dev(out["sum"], out["diff"], out[fk], p, rs, vS,
+                                                        max_hits=max_hits, cols=cols)
+                if width is not None:
+                    self._widths(out, part, fk, out[fk], cols, width)
         return out
 
-    def _measure_plots(self, out, p, ps, with_flagV, max_hits, cond):
+    def _widths(self, out, part, fk, flag, cols, width):
+        """The widths of the columns of `flag` inside the window, and each measured hit's."""
+        import torch
+        from .width import Width, width_dots
+        if self._width is None:
+            self._width = Width(self.device.index or 0)
+        amp_constr, interp = width
+        span, count = self._width.width_dev(out["sum"], flag, amp_constr, interp, True, cols=cols)
+        out[(part, fk, "width")] = (span, count)
+        _, cells, n = out[(part, fk)]
+        max_hits = cells.shape[1]
+        wd = width_dots(span, interp)                                   # [batch][R]
+        col = cells[:, :, 1].to(torch.int64).clamp_(0, span.shape[1] - 1)   # entries past the count are not written
+        got = torch.gather(wd, 1, col) if max_hits else wd[:, :0]
+        live = torch.arange(max_hits, device=wd.device)[None, :] < n[:, :1].to(torch.int64)
+        out[(part, fk, "widthDots")] = torch.where(live, got, torch.full_like(got, float("nan")))
+
+    def _measure_plots(self, out, p, ps, with_flagV, max_hits, cond, width=None):
         import torch
         from .condense import Condense
         if self._cond is None:
@@ -127,9 +161,12 @@ class DmxFrameProcessor:
                 out[(part, fk, "plots")] = (plots, count)
                 out[(part, fk)] = self.meas.measure_dev(out["sum"], out["diff"], out[pk], p, rs, vS,
                                                         max_hits=max_hits, cols=cols)
+                if width is not None:
+                    self._widths(out, part, fk, out[pk], cols, width)
         return out
 
-    def process_records_dev(self, d_stream, nbytes, nframes, with_flagV=True, max_hits=4096, condense=None):
+    def process_records_dev(self, d_stream, nbytes, nframes, with_flagV=True, max_hits=4096, condense=None,
+                            width=None):
         """:307-310 + process_dev from the record bytes: d_stream holds nframes * P consecutive
         legacy records (uint8 on the device, 4-byte aligned; the layout assumed for this waveform,
         see the module docstring), decoded into [nframes][2][P][R] without leaving HBM.  As the main
@@ -140,7 +177,7 @@ class DmxFrameProcessor:
         process_dev measures a batch at one beam position, so the frames are processed in runs of
         consecutive frames that share beamPosNum.  Returns a list with one dict per run:
         process_dev's outputs for the run's frames plus 'frames' (first, end), 'beamPosNum',
-        'frameInd' (int64 [n]) and 'angleCode' (float64 [n][P], host).  condense: as process_dev's."""
+        'frameInd' (int64 [n]) and 'angleCode' (float64 [n][P], host).  condense, width: as process_dev's."""
         from . import _capi as capi
         from .ingest import LegacyIngest
         if self._ingest is None:
@@ -162,7 +199,7 @@ class DmxFrameProcessor:
         for b in range(1, F + 1):
             if b == F or bpn[b] != bpn[a]:
                 out = self.process_dev(echo[a:b], int(bpn[a]), with_flagV=with_flagV, max_hits=max_hits,
-                                       condense=condense)
+                                       condense=condense, width=width)
                 out.update(frames=(a, b), beamPosNum=int(bpn[a]), frameInd=frame_ind[a:b], angleCode=code[a:b])
                 runs.append(out)
                 a = b
