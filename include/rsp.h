@@ -735,6 +735,84 @@ int rsp_spec_width_dev(rsp_ctx* ctx, const float* d_amp, const uint8_t* d_flag /
                        int64_t V, int64_t R, int64_t batch, const rsp_width_params* wp,
                        int32_t* d_span, int32_t* d_count, void* stream);
 
+/* ---- tracking: the plots of successive CPIs joined into tracks ----------------------------- */
+/* DMX_SignalProcessing_main_xzr.m plots each frame's {rEst, vEst, eleAngleEst} against the frame
+ * number and GPS truth (:530-601); the reference ships no stage that says which estimates of
+ * successive frames are one target.  rsp_track_dev is that stage: gated nearest-neighbour
+ * association with fixed smoothing gains and M-of-N confirmation, behind rsp_motion_measure_dev
+ * and on its outputs as they stand.  Like the clutter map it carries state from call to call, and
+ * the state is the caller's memory.
+ *
+ * Input: d_est double [batch][max_hits][3] = {r, v, ele} and d_count int32 [batch][2]; the
+ * n = min(d_count[2b], max_hits) first plots of CPI b are read.  A plot is valid when neither its
+ * r nor its v is NaN.
+ * State: per slot max_tracks entries, d_state_f double [slots][max_tracks][4] = {r, v, ele, 0} and
+ * d_state_i int32 [slots][max_tracks][8] = {id, status, hist, misses, hits, age, last_plot, 0};
+ * status 0 free, 1 tentative, 2 confirmed; hist the hit history, bit 0 the latest CPI; d_meta
+ * int32 [slots][2] = {next_id, cpis}.  A free entry is all zero bytes; reset = zeroing the three
+ * arrays.
+ * Slots: s = d_slot[b] (0 when d_slot is NULL).  The CPIs of a batch are consecutive in time and
+ * are applied in batch order, also when several share a slot.  A CPI whose slot is negative or
+ * >= slots touches no state; its d_assign row is -1 for an invalid plot and 0 otherwise, its
+ * snapshot all zero bytes and its d_tcount row {0, 0, 0, 0, 0, n_valid, 0, 0}.
+ *
+ * One CPI, with h = d_dt[b] (tp->dt when d_dt is NULL), wr = 1/(gate_r*gate_r) and
+ * wv = 1/(gate_v*gate_v) in fp64 on the host; every floating-point operation below is a separate
+ * fp64 operation in the order written (nothing is contracted):
+ *   1 predict    every live track: rp = r + ((rate_sign*v)*h), vp = v.
+ *   2 gate       (t, j) is a candidate when |r_j - rp| <= gate_r and |v_j - vp| <= gate_v, with
+ *                dr = r_j - rp, dv = v_j - vp, cost c = ((dr*dr)*wr) + ((dv*dv)*wv) and key
+ *                (status == 2 ? 0 : 1, c, t, j), ordered lexicographically; t is the entry index.
+ *   3 associate  the candidates in ascending key order, skipping one whose track or plot is taken.
+ *   4 update     matched: r = rp + alpha_r*(r_j - rp), v = vp + alpha_v*(v_j - vp); ele unchanged
+ *                when ele_j is NaN, ele_j when the track's is NaN, else ele + alpha_e*(ele_j - ele);
+ *                hist = (hist<<1)|1, misses = 0, hits += 1, last_plot = j.
+ *                unmatched: r = rp, v = vp, hist <<= 1, misses += 1, last_plot = -1.
+ *                both: age += 1.
+ *   5 confirm    a tentative track with popcount(hist & mask_N) >= M becomes confirmed; then a
+ *     and drop   track that is still tentative is deleted when misses >= drop_tentative or
+ *                age >= N, a confirmed one when misses >= drop_confirmed.  A deleted entry is zeroed.
+ *   6 start      the valid unmatched plots, in plot order, take the free entries in index order
+ *                (those freed in step 5 included): {r_j, v_j, ele_j}, id = ++next_id (ids start
+ *                at 1), tentative (confirmed when M = 1), hist = 1, hits = 1, age = 1, misses = 0,
+ *                last_plot = j.  Plots left without an entry are counted.
+ *                d_assign int32 [batch][max_hits]: the id the plot updated or started, 0 for a
+ *                valid plot that did neither, -1 for an invalid one, 0 at and past n.
+ *   7 record     cpis += 1; d_snap_f / d_snap_i [batch][max_tracks][4] / [8] (both or neither): the
+ *                slot's whole state after the CPI; d_tcount int32 [batch][8] = {live, confirmed,
+ *                started, dropped, not_started, n_valid, matched, 0}.
+ * One workgroup per slot walks its CPIs inside one launch, the table in LDS; the matching runs as
+ * rounds of mutual-best pairs, which the strict total order of the keys makes equal to step 3.
+ * The only atomics are integer minima and counts, whose results do not depend on arrival order,
+ * and no floating-point value is combined across threads: two runs give the same bytes, and a
+ * sequence of CPIs gives the same state and outputs in one batch as in any split into
+ * consecutive calls.
+ * Limits: 56*max_tracks + 32*max_hits <= 163328 bytes of LDS (RSP_ERR_UNSUPPORTED otherwise):
+ * max_hits <= 4656 at max_tracks 256, <= 3312 at 1024.  No buffer may overlap another.  Arguments
+ * are checked before the context is looked at (RSP_ERR_ARG with a message).  Asynchronous on
+ * `stream`; works on any context, the CFAR-only kind included; uses no context scratch. */
+#define RSP_TRACK_MAX_TRACKS 1024
+typedef struct {
+    int32_t max_tracks;        /* 1..1024 track entries per slot */
+    int32_t confirm_m, confirm_n;  /* 1 <= M <= N <= 32 */
+    int32_t drop_tentative;    /* >= 1: consecutive misses that delete a tentative track */
+    int32_t drop_confirmed;    /* >= 1: consecutive misses that delete a confirmed track */
+    int32_t reserved;          /* 0 */
+    double  dt;                /* seconds between consecutive CPIs of a slot (frame time P*prt, :571); > 0 */
+    double  rate_sign;         /* +1 or -1: range moves by rate_sign * v * dt */
+    double  gate_r, gate_v;    /* > 0, in the units of rEst / vEst */
+    double  alpha_r, alpha_v, alpha_e;  /* smoothing gains, each in (0, 1] */
+} rsp_track_params;
+
+int rsp_track_dev(rsp_ctx* ctx, const double* d_est /* [batch][max_hits][3] */,
+                  const int32_t* d_count /* [batch][2] */, int64_t max_hits, int64_t batch,
+                  const rsp_track_params* tp, const int32_t* d_slot /* [batch] or NULL */,
+                  const double* d_dt /* [batch] or NULL */, int32_t slots,
+                  double* d_state_f /* [slots][max_tracks][4] */, int32_t* d_state_i /* [slots][max_tracks][8] */,
+                  int32_t* d_meta /* [slots][2] */, int32_t* d_assign /* [batch][max_hits] */,
+                  double* d_snap_f /* [batch][max_tracks][4] or NULL */, int32_t* d_snap_i /* same, [8] */,
+                  int32_t* d_tcount /* [batch][8] */, void* stream);
+
 /* ---- detection scoring against truth (main_cfar.m's evaluation functions) ---------------- */
 /* The four local functions at the end of MatlabProcess_xuzerui/CFAR_WangCai/main_cfar.m, the
  * reason for its `for T=[5]` threshold loop (:40), over a device-resident batch of flag matrices:

@@ -231,6 +231,26 @@ size_t width_lds_bytes(int V, int interp);
 hipError_t launch_width(const float* amp, const uint8_t* flag, int batch, const WidthArgs& a, int32_t* span,
                         int32_t* count, hipStream_t st);
 
+// Tracking (rsp_track.hip): rsp_track_params with the shape and the gate weights.
+struct TrackArgs {
+    int T, H;              // max_tracks, max_hits
+    int M, N, drop_t, drop_c;
+    int slots;
+    int lanes;             // (launch_track) lanes that share a track's scan of the plots: track_lanes(T)
+    double dt, rate_sign, gate_r, gate_v;
+    double wr, wv;         // 1 / gate^2, fp64 on the host
+    double alpha_r, alpha_v, alpha_e;
+};
+// Dynamic LDS of a track_kernel workgroup, 56 B per entry and 32 B per plot, and the most it may ask for.
+size_t track_lds_bytes(int64_t T, int64_t H);
+size_t track_lds_max();
+// A power of two, 1..64: 1024 threads over the entries rounded up to a power of two.
+int track_lanes(int T);
+// One workgroup per slot walks the batch; slot, dt, snap_f / snap_i may be null.
+hipError_t launch_track(const double* est, const int32_t* count, int64_t batch, const TrackArgs& a, const int32_t* slot,
+                        const double* dt, double* state_f, int32_t* state_i, int32_t* meta, int32_t* assign,
+                        double* snap_f, int32_t* snap_i, int32_t* tcount, hipStream_t st);
+
 // Detection scoring (rsp_score.hip): rsp_score_params with the shape and the resolved pitches.
 struct ScoreArgs {
     int V, R;

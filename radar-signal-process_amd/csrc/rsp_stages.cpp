@@ -1,6 +1,6 @@
 // rsp_stages.cpp -- the C ABI's stage entry points around the chain (include/rsp.h): post-detection
 // measurement, plot condensation, clutter map, Doppler line width, detection scoring, echo pre-filters, target
-// injection, raw-data ingest and the legacy record ingest.  Each validates its arguments and
+// injection, raw-data ingest, the legacy record ingest and tracking.  Each validates its arguments and
 // launches its stage's kernels (rsp_<stage>.hip); the context, the presets and the PC -> MTD ->
 // CFAR chain are in rsp_capi.cpp.
 #include <hip/hip_runtime.h>
@@ -681,5 +681,92 @@ int rsp_ingest_legacy_dev(rsp_ctx* ctx, const uint8_t* d_stream, int64_t nbytes,
     a.beam_stride = beam_stride;
     a.frame_stride = frame_stride;
     HIP_TRY(ctx, rsp::launch_ingest_legacy(d_stream, a, (float2*)d_out, d_angle, d_head, d_status, (hipStream_t)stream));
+    return RSP_OK;
+}
+
+// ------------------------------------------------------------------ tracking
+int rsp_track_dev(rsp_ctx* ctx, const double* d_est, const int32_t* d_count, int64_t max_hits, int64_t batch,
+                  const rsp_track_params* tp, const int32_t* d_slot, const double* d_dt, int32_t slots, double* d_state_f,
+                  int32_t* d_state_i, int32_t* d_meta, int32_t* d_assign, double* d_snap_f, int32_t* d_snap_i,
+                  int32_t* d_tcount, void* stream) {
+    // everything that can be checked on the host comes before the context is looked at
+    const char* who = "rsp_track_dev";
+    if (!tp || !d_count || !d_state_f || !d_state_i || !d_meta || !d_tcount)
+        return fail(ctx, RSP_ERR_ARG, "%s: null argument", who);
+    if (max_hits < 0 || max_hits > 0x7fffffff / 3 || batch < 0 || batch > 0x7fffffff)
+        return fail(ctx, RSP_ERR_ARG, "%s: bad shape max_hits = %lld, batch = %lld", who, (long long)max_hits,
+                    (long long)batch);
+    if (max_hits > 0 && (!d_est || !d_assign)) return fail(ctx, RSP_ERR_ARG, "%s: null argument", who);
+    if ((d_snap_f == nullptr) != (d_snap_i == nullptr))
+        return fail(ctx, RSP_ERR_ARG, "%s: d_snap_f and d_snap_i go together", who);
+    if (tp->max_tracks < 1 || tp->max_tracks > RSP_TRACK_MAX_TRACKS)
+        return fail(ctx, RSP_ERR_ARG, "%s: max_tracks = %d outside 1..%d", who, tp->max_tracks, RSP_TRACK_MAX_TRACKS);
+    if (tp->confirm_m < 1 || tp->confirm_m > tp->confirm_n || tp->confirm_n > 32)
+        return fail(ctx, RSP_ERR_ARG, "%s: confirm %d of %d (1 <= M <= N <= 32)", who, tp->confirm_m, tp->confirm_n);
+    if (tp->drop_tentative < 1 || tp->drop_confirmed < 1)
+        return fail(ctx, RSP_ERR_ARG, "%s: drop counts %d, %d below 1", who, tp->drop_tentative, tp->drop_confirmed);
+    if (tp->reserved != 0) return fail(ctx, RSP_ERR_ARG, "%s: reserved = %d", who, tp->reserved);
+    if (!(tp->dt > 0.0) || !std::isfinite(tp->dt)) return fail(ctx, RSP_ERR_ARG, "%s: dt = %g", who, tp->dt);
+    if (tp->rate_sign != 1.0 && tp->rate_sign != -1.0)
+        return fail(ctx, RSP_ERR_ARG, "%s: rate_sign = %g (+1 or -1)", who, tp->rate_sign);
+    if (!(tp->gate_r > 0.0) || !std::isfinite(tp->gate_r) || !(tp->gate_v > 0.0) || !std::isfinite(tp->gate_v))
+        return fail(ctx, RSP_ERR_ARG, "%s: gate %g, %g", who, tp->gate_r, tp->gate_v);
+    if (!(tp->alpha_r > 0.0 && tp->alpha_r <= 1.0) || !(tp->alpha_v > 0.0 && tp->alpha_v <= 1.0) ||
+        !(tp->alpha_e > 0.0 && tp->alpha_e <= 1.0))
+        return fail(ctx, RSP_ERR_ARG, "%s: alpha %g, %g, %g outside (0, 1]", who, tp->alpha_r, tp->alpha_v, tp->alpha_e);
+    if (slots < 1 || slots > 65535) return fail(ctx, RSP_ERR_ARG, "%s: slots = %d outside 1..65535", who, slots);
+    if (((uintptr_t)d_est | (uintptr_t)d_dt | (uintptr_t)d_state_f | (uintptr_t)d_snap_f) & 7)
+        return fail(ctx, RSP_ERR_ARG, "%s: misaligned argument (doubles: 8 bytes)", who);
+    if (((uintptr_t)d_count | (uintptr_t)d_slot | (uintptr_t)d_state_i | (uintptr_t)d_meta | (uintptr_t)d_assign |
+         (uintptr_t)d_snap_i | (uintptr_t)d_tcount) & 3)
+        return fail(ctx, RSP_ERR_ARG, "%s: misaligned argument (ints: 4 bytes)", who);
+    const int64_t T = tp->max_tracks;
+    // the table and one CPI's plots live in LDS (this also bounds the byte counts below)
+    if (rsp::track_lds_bytes(T, max_hits) > rsp::track_lds_max())
+        return fail(ctx, RSP_ERR_UNSUPPORTED,
+                    "%s: max_tracks %d and max_hits %lld need %zu bytes of LDS (56 per entry, 32 per plot), over %zu", who,
+                    tp->max_tracks, (long long)max_hits, rsp::track_lds_bytes(T, max_hits), rsp::track_lds_max());
+    {
+        struct Buf {
+            const void* p;
+            int64_t n;
+        };
+        const Buf bufs[] = {{d_est, batch * max_hits * 24},   {d_count, batch * 8},          {d_slot, batch * 4},
+                            {d_dt, batch * 8},                {d_state_f, slots * T * 32},   {d_state_i, slots * T * 32},
+                            {d_meta, (int64_t)slots * 8},     {d_assign, batch * max_hits * 4}, {d_snap_f, batch * T * 32},
+                            {d_snap_i, batch * T * 32},       {d_tcount, batch * 32}};
+        constexpr int nb = sizeof(bufs) / sizeof(bufs[0]);
+        for (int i = 0; i < nb; ++i)
+            for (int j = i + 1; j < nb; ++j)
+                if (bufs[i].p && bufs[j].p && bufs[i].n > 0 && bufs[j].n > 0 &&
+                    ranges_overlap(bufs[i].p, bufs[i].n, bufs[j].p, bufs[j].n))
+                    return fail(ctx, RSP_ERR_ARG, "%s: buffers %d and %d overlap", who, i, j);
+    }
+    if (rsp::track_lds_bytes(T, max_hits) > rsp::track_lds_max())
+        return fail(ctx, RSP_ERR_UNSUPPORTED,
+                    "%s: max_tracks %d and max_hits %lld need %zu bytes of LDS (56 per entry, 32 per plot), over %zu", who,
+                    tp->max_tracks, (long long)max_hits, rsp::track_lds_bytes(T, max_hits), rsp::track_lds_max());
+    if (!ctx) return fail(nullptr, RSP_ERR_ARG, "%s: null ctx", who);
+    if (batch == 0) return RSP_OK;
+    if (!set_device(ctx)) return fail(ctx, RSP_ERR_HIP, "hipSetDevice failed");
+    rsp::TrackArgs a{};
+    a.T = tp->max_tracks;
+    a.H = (int)max_hits;
+    a.M = tp->confirm_m;
+    a.N = tp->confirm_n;
+    a.drop_t = tp->drop_tentative;
+    a.drop_c = tp->drop_confirmed;
+    a.slots = slots;
+    a.dt = tp->dt;
+    a.rate_sign = tp->rate_sign;
+    a.gate_r = tp->gate_r;
+    a.gate_v = tp->gate_v;
+    a.wr = 1.0 / (tp->gate_r * tp->gate_r);
+    a.wv = 1.0 / (tp->gate_v * tp->gate_v);
+    a.alpha_r = tp->alpha_r;
+    a.alpha_v = tp->alpha_v;
+    a.alpha_e = tp->alpha_e;
+    HIP_TRY(ctx, rsp::launch_track(d_est, d_count, batch, a, d_slot, d_dt, d_state_f, d_state_i, d_meta, d_assign,
+                                   d_snap_f, d_snap_i, d_tcount, (hipStream_t)stream));
     return RSP_OK;
 }

@@ -34,7 +34,7 @@ EXPORTS = ("rsp_version", "rsp_create", "rsp_destroy", "rsp_last_error", "rsp_se
            "rsp_pc_mtd_cfar_f64", "rsp_cfar_f64", "rsp_set_range_concat", "rsp_score_dev", "rsp_score_summary",
            "rsp_set_pc_prune", "rsp_set_lane_chunks", "rsp_pc_plan", "rsp_scr_dev", "rsp_inject_dev", "rsp_scr_gain",
            "rsp_cfar_plan", "rsp_legacy_record_bytes", "rsp_ingest_legacy_dev", "rsp_condense_dev", "rsp_cmap_dev",
-           "rsp_cmap_plan", "rsp_spec_width_dev")
+           "rsp_cmap_plan", "rsp_spec_width_dev", "rsp_track_dev")
 RSP_NKERNELS = 4
 KERNEL_NAMES = ("pc_kernel", "mtd_kernel", "cfar_r_kernel", "cfar_v_kernel")
 
@@ -121,6 +121,16 @@ RSP_WIDTH_MIN_V, RSP_WIDTH_MAX_V = 4, 2048
 class rsp_width_params(C.Structure):
     _fields_ = [("amp_constr", C.c_double), ("interp", C.c_int32), ("shift", C.c_int32), ("ld", C.c_int64),
                 ("cpi_stride", C.c_int64)]
+
+
+RSP_TRACK_MAX_TRACKS = 1024
+
+
+class rsp_track_params(C.Structure):
+    _fields_ = [("max_tracks", C.c_int32), ("confirm_m", C.c_int32), ("confirm_n", C.c_int32),
+                ("drop_tentative", C.c_int32), ("drop_confirmed", C.c_int32), ("reserved", C.c_int32),
+                ("dt", C.c_double), ("rate_sign", C.c_double), ("gate_r", C.c_double), ("gate_v", C.c_double),
+                ("alpha_r", C.c_double), ("alpha_v", C.c_double), ("alpha_e", C.c_double)]
 
 
 class rsp_score_params(C.Structure):
@@ -265,6 +275,9 @@ def load_library(path=None):
     lib.rsp_cmap_plan.argtypes = [vp, i64, i64, C.POINTER(rsp_cmap_params), C.POINTER(rsp_cmap_plan_t)]
     lib.rsp_spec_width_dev.restype = C.c_int
     lib.rsp_spec_width_dev.argtypes = [vp, vp, vp, i64, i64, i64, C.POINTER(rsp_width_params), vp, vp, vp]
+    lib.rsp_track_dev.restype = C.c_int
+    lib.rsp_track_dev.argtypes = [vp, vp, vp, i64, i64, C.POINTER(rsp_track_params), vp, vp, i32, vp, vp, vp, vp, vp,
+                                  vp, vp, vp]
     lib.rsp_score_dev.restype = C.c_int
     lib.rsp_score_dev.argtypes = [vp, vp, vp, i64, i64, i64, C.POINTER(rsp_score_params), vp, vp, vp]
     lib.rsp_score_summary.restype = C.c_int

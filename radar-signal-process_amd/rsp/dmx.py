@@ -67,10 +67,14 @@ class DmxFrameProcessor:
         self._ingest = None
         self._cond = None
         self._width = None
+        self._tracker = None
+        self._track_opts = None
 
     def close(self):
         self.eng.close()
         self.meas.close()
+        if self._tracker is not None:
+            self._tracker.close()
         if self._cond is not None:
             self._cond.close()
         if self._width is not None:
@@ -78,7 +82,45 @@ class DmxFrameProcessor:
         if self._ingest is not None:
             self._ingest.close()
 
-    def process_dev(self, echo, beamPosNum, with_flagV=True, max_hits=4096, condense=None, width=None):
+    # the tracker's slot of each (part, kind)
+    TRACK_SLOTS = {("short", "flag"): 0, ("long", "flag"): 1, ("short", "flagV"): 2, ("long", "flagV"): 3}
+
+    def reset_tracks(self):
+        """Forget every track of process_dev(track=...)."""
+        if self._tracker is not None:
+            self._tracker.reset()
+
+    def _track_options(self, track):
+        """track=dict(...) as the Tracker's keyword arguments; dt defaults to the frame time P / prf."""
+        track = dict(track)
+        opts = dict(gate=tuple(track.pop("gate")) if "gate" in track else None,
+                    alpha=tuple(track.pop("alpha", (0.5, 0.5, 0.5))), confirm=tuple(track.pop("confirm", (3, 5))),
+                    drop=tuple(track.pop("drop", (2, 4))), max_tracks=int(track.pop("max_tracks", 256)),
+                    dt=float(track.pop("dt", self.spec.P / self.spec.radar["prf"])),
+                    rate_sign=float(track.pop("rate_sign", 1.0)))
+        if track:
+            raise TypeError("process_dev: track takes gate, alpha, confirm, drop, max_tracks, dt and rate_sign, not %s"
+                            % sorted(track))
+        if opts["gate"] is None:
+            raise TypeError("process_dev: track needs gate=(gate_r, gate_v)")
+        return opts
+
+    def _tracks(self, out, opts, with_flagV):
+        """out[(part, kind, 'tracks')] of every measured (part, kind), each on its own slot."""
+        from .track import Tracker
+        if self._tracker is None or opts != self._track_opts:
+            if self._tracker is not None:
+                self._tracker.close()
+            self._tracker = Tracker(self.device.index or 0, slots=len(self.TRACK_SLOTS), **opts)
+            self._track_opts = opts
+        for (part, fk), slot in self.TRACK_SLOTS.items():
+            if fk == "flagV" and not with_flagV:
+                continue
+            est, _, count = out[(part, fk)]
+            out[(part, fk, "tracks")] = self._tracker.update_dev(est, count, slot=slot)
+        return out
+
+    def process_dev(self, echo, beamPosNum, with_flagV=True, max_hits=4096, condense=None, width=None, track=None):
         """echo: complex64 [batch][2][P][R] (left, right) on the device.  Returns a dict of
         device outputs: the planes (sum, diff, flag, flagV) and, per part ('short', 'long') and
         flag kind ('flag', 'flagV'), (est, cells, count) as Measure.measure_dev gives them.
@@ -96,8 +138,20 @@ class DmxFrameProcessor:
         of the sum plane (shift = 1: these planes carry no fftshift), on the columns of the flag
         plane that was measured (the peak plane when condensing), and out[(part, kind,
         'widthDots')], float64 [batch][max_hits]: the width of each measured hit's column, gathered
-        through the measurement's cells, NaN past the count."""
+        through the measurement's cells, NaN past the count.
+
+        track = dict(gate=(gate_r, gate_v), alpha=(ar, av, ae), confirm=(M, N), drop=(dt, dc),
+        max_tracks=256, dt=P/prf, rate_sign=1.0): every (part, kind) that is measured also gets
+        out[(part, kind, 'tracks')] = (assign, snap_f, snap_i, tcount) of Tracker.update_dev over
+        that key's (est, count).  The processor owns one Tracker with a slot per (part, kind)
+        (TRACK_SLOTS); its state persists from call to call, so the batches of successive calls are
+        consecutive in time, and reset_tracks() clears it.  A call whose options differ from the
+        previous call's starts a new Tracker.  Without condense every hit of a target starts its
+        own track (a target lights several cells): track the plots, not the hits.  track=None
+        leaves every other output as it is."""
         import torch
+        if track is not None:
+            track = self._track_options(track)
         if width is not None:
             width = dict(width)
             wopt = (width.pop("amp_constr", -6.0), width.pop("interp", 4))
@@ -118,14 +172,15 @@ class DmxFrameProcessor:
                              o["beamAngleStep"], o["eleAngleComp"], o["eleAngleSysErr"], self.spec.radar["M0"])
         ps = self.spec.cfar_segments[0][1]
         if condense is not None:
-            return self._measure_plots(out, p, ps, with_flagV, max_hits, dict(condense), width)
+            out = self._measure_plots(out, p, ps, with_flagV, max_hits, dict(condense), width)
+            return out if track is None else self._tracks(out, track, with_flagV)
         for fk in ("flag", "flagV") if with_flagV else ("flag",):
             for part, cols, rs in (("short", (0, ps), rS), ("long", (ps, self.spec.R_out), rL)):
                 out[(part, fk)] = self.meas.measure_dev(out["sum"], out["diff"], out[fk], p, rs, vS,
                                                         max_hits=max_hits, cols=cols)
                 if width is not None:
                     self._widths(out, part, fk, out[fk], cols, width)
-        return out
+        return out if track is None else self._tracks(out, track, with_flagV)
 
     def _widths(self, out, part, fk, flag, cols, width):
         """The widths of the columns of `flag` inside the window, and each measured hit's."""
@@ -166,7 +221,7 @@ class DmxFrameProcessor:
         return out
 
     def process_records_dev(self, d_stream, nbytes, nframes, with_flagV=True, max_hits=4096, condense=None,
-                            width=None):
+                            width=None, track=None):
         """:307-310 + process_dev from the record bytes: d_stream holds nframes * P consecutive
         legacy records (uint8 on the device, 4-byte aligned; the layout assumed for this waveform,
         see the module docstring), decoded into [nframes][2][P][R] without leaving HBM.  As the main
@@ -177,7 +232,9 @@ class DmxFrameProcessor:
         process_dev measures a batch at one beam position, so the frames are processed in runs of
         consecutive frames that share beamPosNum.  Returns a list with one dict per run:
         process_dev's outputs for the run's frames plus 'frames' (first, end), 'beamPosNum',
-        'frameInd' (int64 [n]) and 'angleCode' (float64 [n][P], host).  condense, width: as process_dev's."""
+        'frameInd' (int64 [n]) and 'angleCode' (float64 [n][P], host).  condense, width, track: as
+        process_dev's; the runs at different beamPosNum feed the same track slots, because the frames
+        are consecutive in time and eleAngleEst is absolute."""
         from . import _capi as capi
         from .ingest import LegacyIngest
         if self._ingest is None:
@@ -199,7 +256,7 @@ class DmxFrameProcessor:
         for b in range(1, F + 1):
             if b == F or bpn[b] != bpn[a]:
                 out = self.process_dev(echo[a:b], int(bpn[a]), with_flagV=with_flagV, max_hits=max_hits,
-                                       condense=condense, width=width)
+                                       condense=condense, width=width, track=track)
                 out.update(frames=(a, b), beamPosNum=int(bpn[a]), frameInd=frame_ind[a:b], angleCode=code[a:b])
                 runs.append(out)
                 a = b
