@@ -318,6 +318,19 @@ int rsp_set_pc_split(rsp_ctx* ctx, int32_t enable);
  * RSP_ERR_UNSUPPORTED on a context without the specialised PC kernels (nothing to select). */
 int rsp_set_pc_prune(rsp_ctx* ctx, int32_t enable);
 
+/* Rows per workgroup of the 4096-point pulse-compression rows (additions within ABI 5): with
+ * n = 2 or 4 a workgroup of those rows (v2 at 4096 range bins and above, DMX at 4096) runs n
+ * consecutive rows -- or overlap-save blocks -- one after the other and loads the replica spectrum
+ * and the twiddles once for all of them, not once per row.  n = 1 is one row per workgroup;
+ * n = 0 returns to the library default.  Every stored value is bit-identical for every n.
+ * Other row lengths, and 4096-point rows whose launch also runs the FIR segment, keep one row per
+ * workgroup whatever n is.
+ * RSP_ERR_UNSUPPORTED on a context without the specialised PC kernels; RSP_ERR_ARG for any other n. */
+int rsp_set_pc_rows(rsp_ctx* ctx, int32_t n);
+/* The rows per workgroup the context's next pulse-compression launch of 4096-point rows will run
+ * (1, 2 or 4: the launcher's own choice); 1 where no launch takes the multi-row path. */
+int rsp_get_pc_rows(rsp_ctx* ctx);
+
 /* The pulse-compression launches the context will issue, as chosen from the segment lengths and
  * the two switches above (read-only; an addition within ABI 5) -- for tests and tools that must
  * know which kernel path a geometry takes.  One entry per matched-filter segment, in segment

@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "rsp_ctx.h"
+#include "rsp_pcplan.h"
 
 using rsp::make_window;
 using rsp::scratch_acquire;
@@ -862,16 +863,28 @@ static rsp::PcMfArgs pc_launch_args(const rsp_ctx* ctx, size_t i, int64_t rows) 
     return a;
 }
 
+// Rows per long-row workgroup slot asked of the launcher: rsp_set_pc_rows, else the library default.
+// Dev A/B: RSP_PC_ROWS=1|2|4 replaces the default (read once).
+static int pc_rows_want(const rsp_ctx* ctx) {
+    static const int dflt = [] {
+        const char* v = getenv("RSP_PC_ROWS");
+        const int n = v ? atoi(v) : 0;
+        return rsp::pc_rows_valid(n) ? n : rsp::kPcRowsDefault;
+    }();
+    return ctx->pc_rows ? ctx->pc_rows : dflt;
+}
+
 static hipError_t run_pc_rows(rsp_ctx* ctx, const void* ein, int dtype, float2* out, int64_t rows, hipStream_t s) {
+    const int want = ctx->pc_v2 ? pc_rows_want(ctx) : 1;
     if (!ctx->pc_v2)
         return timed(ctx, RSP_K_PC, s, [&] { return rsp::launch_pc(ein, dtype, out, rows, ctx->pc, ctx->pc_lds, s); });
     if (pc_fused(ctx)) {
         const rsp::PcMfArgs a1 = pc_launch_args(ctx, 0, rows), a2 = pc_launch_args(ctx, 1, rows);
-        return timed(ctx, RSP_K_PC, s, [&] { return rsp::launch_pc_mf(ein, dtype, out, a1, &a2, s); });
+        return timed(ctx, RSP_K_PC, s, [&] { return rsp::launch_pc_mf(ein, dtype, out, a1, &a2, want, s); });
     }
     for (size_t i = 0; i < ctx->pc_mf.size(); ++i) {
         const rsp::PcMfArgs a = pc_launch_args(ctx, i, rows);
-        hipError_t e = timed(ctx, RSP_K_PC, s, [&] { return rsp::launch_pc_mf(ein, dtype, out, a, nullptr, s); });
+        hipError_t e = timed(ctx, RSP_K_PC, s, [&] { return rsp::launch_pc_mf(ein, dtype, out, a, nullptr, want, s); });
         if (e != hipSuccess) return e;
     }
     return hipSuccess;
@@ -985,6 +998,34 @@ int rsp_set_pc_prune(rsp_ctx* ctx, int32_t enable) {
         return fail(ctx, RSP_ERR_UNSUPPORTED, "rsp_set_pc_prune: this context has no specialised PC path");
     ctx->pc_prune = enable != 0;
     return RSP_OK;
+}
+
+int rsp_set_pc_rows(rsp_ctx* ctx, int32_t n) {
+    if (!ctx) return fail(nullptr, RSP_ERR_ARG, "rsp_set_pc_rows: null ctx");
+    if (ctx->cfar_only) return fail(ctx, RSP_ERR_ARG, "rsp_set_pc_rows: CFAR-only context");
+    if (!ctx->pc_v2)   // the generic PC path runs one row per workgroup
+        return fail(ctx, RSP_ERR_UNSUPPORTED, "rsp_set_pc_rows: this context has no specialised PC path");
+    if (n != 0 && !rsp::pc_rows_valid(n)) return fail(ctx, RSP_ERR_ARG, "rsp_set_pc_rows: %d is not 0, 1, 2 or 4", (int)n);
+    ctx->pc_rows = n;
+    return RSP_OK;
+}
+
+// What the next launches will use: the launcher's own choice (pc_rows_select) for each launch of
+// run_pc_rows, the largest of them where a context has several.
+int rsp_get_pc_rows(rsp_ctx* ctx) {
+    if (!ctx || ctx->cfar_only || !ctx->pc_v2) return 1;
+    const int want = pc_rows_want(ctx);
+    if (pc_fused(ctx)) {
+        const rsp::PcMfArgs a1 = pc_launch_args(ctx, 0, 1), a2 = pc_launch_args(ctx, 1, 1);
+        return rsp::pc_rows_select(a1, &a2, want);
+    }
+    int rows = 1;
+    for (size_t i = 0; i < ctx->pc_mf.size(); ++i) {
+        const rsp::PcMfArgs a = pc_launch_args(ctx, i, 1);
+        const int r = rsp::pc_rows_select(a, nullptr, want);
+        if (r > rows) rows = r;
+    }
+    return rows;
 }
 
 int rsp_set_prefilter(rsp_ctx* ctx, const float* gain, int32_t mti_lag) {

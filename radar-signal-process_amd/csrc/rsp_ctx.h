@@ -42,6 +42,7 @@ struct rsp_ctx {
     int nlane_cpis = 0;                       // 0: equal chunks / the default split
     // rsp_set_pc_prune: pruned PC kernel instances where built (dev A/B: RSP_PC_PRUNE=0 starts off)
     bool pc_prune = [] { const char* v = getenv("RSP_PC_PRUNE"); return !(v && *v == '0'); }();
+    int pc_rows = 0;   // rsp_set_pc_rows: rows per long-row workgroup slot; 0: the library default
     rsp::MtdArgs mtd{};
     int64_t V = 0;                      // Doppler rows (rsp_params.mtd_nfft or P)
     int beams = 1;                      // 2: DMX left/right pair

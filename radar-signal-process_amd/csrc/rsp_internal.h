@@ -398,9 +398,13 @@ bool pc_pair_supported(int nfft1, int nfft2);
 // The pruned kernel instance launch_pc_mf runs for (a1, a2), as 0x<ZIN1><ZOUT1><ZIN2><ZOUT2>
 // (pc_row); 0: the generic instance
 int pc_prune_select(const PcMfArgs& a1, const PcMfArgs* a2);
-// a2 == nullptr: one segment; otherwise both segments (a1.mf.nfft, a2->mf.nfft) in one launch
+// Consecutive units a long-row workgroup slot of launch_pc_mf(a1, a2) walks when `want` (1, 2, 4)
+// are asked for: `want` where the multi-row path exists (4096-point rows without a FIR), else 1
+int pc_rows_select(const PcMfArgs& a1, const PcMfArgs* a2, int want);
+// a2 == nullptr: one segment; otherwise both segments (a1.mf.nfft, a2->mf.nfft) in one launch;
+// pc_rows: rows per long-row workgroup slot asked for (pc_rows_select decides)
 hipError_t launch_pc_mf(const void* echo, int dtype, float2* out, const PcMfArgs& a1, const PcMfArgs* a2,
-                        hipStream_t s);
+                        int pc_rows, hipStream_t s);
 hipError_t launch_mtd(const float2* pc, float* rdm, uint8_t* flagV, int ncpi, const MtdArgs& a,
                       hipStream_t s);
 // Doppler CFAR straight from an RDM ([ncpi][V][R] fp32) for rsp_cfar.

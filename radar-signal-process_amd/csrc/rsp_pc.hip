@@ -14,6 +14,7 @@
 #include "rsp_buf.h"
 #include "rsp_diag.h"
 #include "rsp_internal.h"
+#include "rsp_pcplan.h"
 
 namespace rsp {
 
@@ -406,6 +407,85 @@ __device__ __forceinline__ void pc_row(const TIn* __restrict__ echo, float2* __r
 }
 
 
+// ROWS consecutive units of a wave-uniform matched-filter segment without a FIR, one after the
+// other through the same G threads (rsp_set_pc_rows; the 4096-point rows).  The twiddles and the
+// thread's spectrum slice are the same for every row of a launch: they are loaded once, ahead of
+// a row loop that is not unrolled, instead of once per row (24 of a long row's 50 vector-memory
+// instructions).  Inside the loop a row does exactly what pc_row does -- the same operations on
+// the same operands in the same order, so every stored value keeps its bits.
+//
+// Every unit-derived value that reaches a buffer resource goes through readfirstlane, as in
+// pc_row.  A unit past the end runs as an invalid row (num_records 0: loads return 0, stores are
+// dropped) and still takes every barrier.
+//
+// The exchange slot is reused by the next row without a barrier of its own: fft_reg_w puts a
+// barrier (xsync, "WAR") in front of every exchange write, so row k+1's first write waits for
+// every wave to have arrived there, which each does only after its last exchange read of row k
+// (lds_barrier waits lgkmcnt(0) before s_barrier).  (With RSP_DIAG_PC_NOFFT there is no exchange.)
+template <typename TIn, int N, int G, int ROWS, int ZIN = 0, int ZOUT = 0>
+__device__ __forceinline__ void pc_rows(const TIn* __restrict__ echo, float2* __restrict__ out,
+                                        const PcMfArgs& a, int u0, int t, float2* buf) {
+    constexpr int E = N / G;
+    static_assert(G % 64 == 0 && G > 64, "rows of whole waves, exchanged through the workgroup barrier");
+    static_assert(N <= 4096, "the spectrum slice stays in registers");
+    static_assert(ZIN >= 0 && ZIN < E && ZOUT >= 0 && ZOUT < E, "a row keeps at least one slice");
+    constexpr int EI = E - ZIN, EO = E - ZOUT;
+    constexpr uint32_t ES = sizeof(TIn);
+    const int e0 = t;
+    const float2* __restrict__ tw = a.mf.tw;
+    const auto hr = buf_rsrc(a.mf.H, (uint32_t)N * 8u);
+    constexpr int NW = tw_regs<N, E>() > 0 ? tw_regs<N, E>() : 1;
+    float2 w[NW];
+    tw_preload<N, G, 1, E, 0, NW>(w, t, tw);
+    float2 hs[E];
+#pragma unroll
+    for (int m = 0; m < E; ++m) hs[m] = buf_ld_f2(hr, (uint32_t)e0 * 8u, (uint32_t)(G * m) * 8u);
+    const int ns = a.nsub > 1 ? a.nsub : 1;
+#pragma unroll 1
+    for (int k = 0; k < ROWS; ++k) {
+        const int unit = __builtin_amdgcn_readfirstlane(u0 + k);
+        const int row = __builtin_amdgcn_readfirstlane(unit / ns);
+        const int sub = __builtin_amdgcn_readfirstlane(unit % ns);
+        const bool valid = row < a.rows;
+        const TIn* x = echo + (size_t)diag_pc_src_row(row) * a.R;
+        const bool st_ok = valid && !kDiagPcNoStore;
+        float2* y = out + (size_t)row * a.R_out;
+        int in_start = a.mf.in_start, in_len = a.mf.in_len;
+        int out_start = a.mf.out_start, out_len = a.mf.out_len;
+        if (a.nsub > 1) {   // overlap-save sub-block: shifted input and output windows
+            const int off = sub * a.sub_step;
+            in_start = __builtin_amdgcn_readfirstlane(in_start + off);
+            out_start = __builtin_amdgcn_readfirstlane(out_start + off);
+            in_len = __builtin_amdgcn_readfirstlane(max(0, min(in_len - off, N)));
+            out_len = __builtin_amdgcn_readfirstlane(max(0, min(out_len - off, a.sub_step)));
+        }
+        float2 u[E];
+        const auto xr = buf_rsrc(x + in_start, valid ? (uint32_t)in_len * ES : 0u);
+#pragma unroll
+        for (int m = 0; m < EI; ++m) u[m] = buf_ld_c((const TIn*)nullptr, xr, (uint32_t)e0 * ES, (uint32_t)(G * m) * ES);
+#pragma unroll
+        for (int m = EI; m < E; ++m) u[m] = make_float2(0.f, 0.f);
+        if (a.gain) {   // fused iSTC (rsp_set_prefilter): echo column n times gain[n]
+            const auto gr = buf_rsrc(a.gain + in_start, (uint32_t)in_len * 4u);
+#pragma unroll
+            for (int m = 0; m < EI; ++m) u[m] = cscale(u[m], buf_ld_f(gr, (uint32_t)e0 * 4u, (uint32_t)(G * m) * 4u));
+        }
+        if (a.nzero > 0 && valid && sub == 0) {   // columns no segment covers stay 0 (as pc_row, no FIR)
+            for (int z = 0; z < a.nzero; ++z)
+                for (int c = a.zero_lo[z] + t; c < a.zero_hi[z]; c += G) y[c] = make_float2(0.f, 0.f);
+        }
+        if constexpr (!kDiagPcNoFft) fft_reg_w<N, G, 1, E, 0, NW, false, ZIN, 0>(u, buf, t, w);
+#pragma unroll
+        for (int m = 0; m < E; m += 2)   // conj(X.*H), 1/N in H (E is even)
+            cmul2_conj(u[m], u[m], hs[m], u[m + 1], u[m + 1], hs[m + 1]);
+        if constexpr (!kDiagPcNoFft) fft_reg_w<N, G, 1, E, 0, NW, false, 0, ZOUT>(u, buf, t, w);
+        const auto yr = buf_rsrc(y + out_start, st_ok ? (uint32_t)out_len * 8u : 0u);
+#pragma unroll
+        for (int m = 0; m < EO; ++m) buf_st_f2(cconj(u[m]), yr, (uint32_t)e0 * 8u, (uint32_t)(G * m) * 8u);
+    }
+}
+
+
 // Workgroup size shared by a pair of segment lengths: both run T threads (RPB = T/G rows).
 template <int N1, int N2>
 struct PairCfg {
@@ -422,8 +502,11 @@ struct PairCfg {
 // `bid` is the block's index among the PC blocks of the launch.
 // PR packs the pruned slice counts of the two segments, one hex digit each: 0x<ZIN1><ZOUT1><ZIN2><ZOUT2>
 // (pc_row); 0 is the generic instance.
+// ROWS > 1 (the 4096-point rows without a FIR only): a long-row workgroup walks ROWS consecutive
+// units (pc_rows); the launcher sizes the long blocks by RPB * ROWS (pc_blocks).
+constexpr bool pc_rows_built(int n, int rows) { return rows == 1 || (n == 4096 && (rows == 2 || rows == 4)); }
 constexpr int pc_prune_code(int zi1, int zo1, int zi2, int zo2) { return zi1 << 12 | zo1 << 8 | zi2 << 4 | zo2; }
-template <typename TIn, int N1, int N2, int PR = 0>
+template <typename TIn, int N1, int N2, int PR = 0, int ROWS = 1>
 __device__ __forceinline__ void pc_mf_block(const TIn* __restrict__ echo, float2* __restrict__ out, const PcMfArgs& a1,
                                             const PcMfArgs& a2, int nblk2, int bid, float2* lds) {
     constexpr int M2 = N2 ? N2 : N1;
@@ -437,8 +520,14 @@ __device__ __forceinline__ void pc_mf_block(const TIn* __restrict__ echo, float2
             const int grp = threadIdx.x / G, t = threadIdx.x % G;
             const int ns = a2.nsub > 1 ? a2.nsub : 1;
             const int u = bid * PC::RPB2 + grp;
-            pc_row<TIn, N2, G, G == 64, (PR >> 4 & 15), (PR & 15)>(echo, out, a2, u / ns, t,
-                                                                   lds + grp * PcCfg<N2>::SLOT, u % ns);
+            if constexpr (ROWS > 1) {
+                static_assert(pc_rows_built(N2, ROWS), "no multi-row path for this length");
+                pc_rows<TIn, N2, G, ROWS, (PR >> 4 & 15), (PR & 15)>(echo, out, a2, u * ROWS, t,
+                                                                     lds + grp * PcCfg<N2>::SLOT);
+            } else {
+                pc_row<TIn, N2, G, G == 64, (PR >> 4 & 15), (PR & 15)>(echo, out, a2, u / ns, t,
+                                                                       lds + grp * PcCfg<N2>::SLOT, u % ns);
+            }
             return;
         }
     }
@@ -448,17 +537,23 @@ __device__ __forceinline__ void pc_mf_block(const TIn* __restrict__ echo, float2
     const int u = b * PC::RPB1 + grp, ns = a1.nsub > 1 ? a1.nsub : 1;   // (no FIR when ns > 1)
     // a row of one wave (G == 64) synchronises its exchanges within the wave: the rows of a
     // workgroup run independently instead of in barrier lockstep
-    pc_row<TIn, N1, G, G == 64, (PR >> 12 & 15), (PR >> 8 & 15)>(echo, out, a1, u / ns, t,
-                                                                 lds + grp * PcCfg<N1>::SLOT, u % ns);
+    if constexpr (N2 == 0 && ROWS > 1) {   // a single-segment launch of long rows
+        static_assert(pc_rows_built(N1, ROWS), "no multi-row path for this length");
+        pc_rows<TIn, N1, G, ROWS, (PR >> 12 & 15), (PR >> 8 & 15)>(echo, out, a1, u * ROWS, t,
+                                                                   lds + grp * PcCfg<N1>::SLOT);
+    } else {
+        pc_row<TIn, N1, G, G == 64, (PR >> 12 & 15), (PR >> 8 & 15)>(echo, out, a1, u / ns, t,
+                                                                     lds + grp * PcCfg<N1>::SLOT, u % ns);
+    }
 }
 
-template <typename TIn, int N1, int N2, int PR = 0>
+template <typename TIn, int N1, int N2, int PR = 0, int ROWS = 1>
 __global__ __launch_bounds__((PairCfg<N1, (N2 ? N2 : N1)>::T), RSP_DIAG_PC_WAVES) void pc_mf_kernel(
     const TIn* __restrict__ echo, float2* __restrict__ out, PcMfArgs a1, PcMfArgs a2, int nblk2) {
     extern __shared__ __attribute__((aligned(16))) float2 lds[];
     RSP_STAMP(0, 0, false);
     RSP_STAMP_RT(0, 8);
-    pc_mf_block<TIn, N1, N2, PR>(echo, out, a1, a2, nblk2, (int)blockIdx.x, lds);
+    pc_mf_block<TIn, N1, N2, PR, ROWS>(echo, out, a1, a2, nblk2, (int)blockIdx.x, lds);
 }
 
 
@@ -473,21 +568,22 @@ bool pc_mf_supported(int nfft, int fir_stage_len) {
     }
 }
 
-template <typename TIn, int N1, int N2, int PR = 0>
+template <typename TIn, int N1, int N2, int PR = 0, int ROWS = 1>
 static hipError_t launch_pc_mf_n(const TIn* echo, float2* out, const PcMfArgs& a1, const PcMfArgs* a2,
                                  hipStream_t s) {
     constexpr int M2 = N2 ? N2 : N1;
     using PC = PairCfg<N1, M2>;
     static LaunchOnce once;
     constexpr size_t lds = PC::lds + kDiagPcLdsExtra;
-    hipError_t e = lds_attr(once, (const void*)pc_mf_kernel<TIn, N1, N2, PR>, lds);
+    hipError_t e = lds_attr(once, (const void*)pc_mf_kernel<TIn, N1, N2, PR, ROWS>, lds);
     if (e != hipSuccess) return e;
+    // ROWS applies to the long rows: segment 2 of a pair, segment 1 of a single-segment launch
     const int u1 = a1.rows * (a1.nsub > 1 ? a1.nsub : 1);
-    const int nblk1 = (u1 + PC::RPB1 - 1) / PC::RPB1;
+    const int nblk1 = pc_blocks(u1, PC::RPB1, N2 ? 1 : ROWS);
     const int u2 = a2 ? a2->rows * (a2->nsub > 1 ? a2->nsub : 1) : 0;
-    const int nblk2 = N2 ? (u2 + PC::RPB2 - 1) / PC::RPB2 : 0;
+    const int nblk2 = N2 ? pc_blocks(u2, PC::RPB2, ROWS) : 0;
     dim3 grid((unsigned)(nblk1 + nblk2)), block(PC::T);
-    hipLaunchKernelGGL((pc_mf_kernel<TIn, N1, N2, PR>), grid, block, lds, s, echo, out, a1, a2 ? *a2 : a1, nblk2);
+    hipLaunchKernelGGL((pc_mf_kernel<TIn, N1, N2, PR, ROWS>), grid, block, lds, s, echo, out, a1, a2 ? *a2 : a1, nblk2);
     return hipGetLastError();
 }
 
@@ -507,15 +603,40 @@ int pc_prune_select(const PcMfArgs& a1, const PcMfArgs* a2) {
     return 0;
 }
 
-template <typename TIn>
-static hipError_t launch_pc_mf_t(const TIn* echo, float2* out, const PcMfArgs& a1, const PcMfArgs* a2,
+// Rows per long-row workgroup slot a launch of (a1, a2) runs when `want` are asked for -- the
+// launcher's choice, and what rsp_get_pc_rows reports.  The multi-row path exists for 4096-point
+// rows without a FIR: the long segment of the 1024/4096 pair and a single-segment launch.
+int pc_rows_select(const PcMfArgs& a1, const PcMfArgs* a2, int want) {
+    if (!pc_rows_valid(want) || want == 1) return 1;
+    if (a2) return a1.mf.nfft == 1024 && a2->mf.nfft == 4096 && !a2->do_fir ? want : 1;
+    return a1.mf.nfft == 4096 && !a1.do_fir ? want : 1;
+}
+
+// the 4096-point long rows at 1, 2 or 4 rows per workgroup slot
+template <typename TIn, int N1, int N2, int PR>
+static hipError_t launch_pc_mf_r(const TIn* echo, float2* out, const PcMfArgs& a1, const PcMfArgs* a2, int rows,
                                  hipStream_t s) {
+    switch (rows) {
+        case 4: return launch_pc_mf_n<TIn, N1, N2, PR, 4>(echo, out, a1, a2, s);
+        case 2: return launch_pc_mf_n<TIn, N1, N2, PR, 2>(echo, out, a1, a2, s);
+        default: return launch_pc_mf_n<TIn, N1, N2, PR, 1>(echo, out, a1, a2, s);
+    }
+}
+
+template <typename TIn>
+static hipError_t launch_pc_mf_t(const TIn* echo, float2* out, const PcMfArgs& a1, const PcMfArgs* a2, int want,
+                                 hipStream_t s) {
+    const int rows = pc_rows_select(a1, a2, want);
     switch (pc_prune_select(a1, a2)) {
         case pc_prune_code(4, 4, 3, 3):
-            return launch_pc_mf_n<TIn, 1024, 4096, pc_prune_code(4, 4, 3, 3)>(echo, out, a1, a2, s);
+            return launch_pc_mf_r<TIn, 1024, 4096, pc_prune_code(4, 4, 3, 3)>(echo, out, a1, a2, rows, s);
         case pc_prune_code(4, 4, 0, 2):
-            return launch_pc_mf_n<TIn, 1024, 4096, pc_prune_code(4, 4, 0, 2)>(echo, out, a1, a2, s);
+            return launch_pc_mf_r<TIn, 1024, 4096, pc_prune_code(4, 4, 0, 2)>(echo, out, a1, a2, rows, s);
         default: break;   // anything else runs the generic instance
+    }
+    if (rows > 1) {
+        if (a2) return launch_pc_mf_r<TIn, 1024, 4096, 0>(echo, out, a1, a2, rows, s);
+        return launch_pc_mf_r<TIn, 4096, 0, 0>(echo, out, a1, nullptr, rows, s);
     }
     // fused pairs of the built-in presets (v2 at 1024..16384 range bins, legacy)
     RSP_PAIR(1024, 1024);
@@ -555,10 +676,10 @@ bool pc_pair_supported(int n1, int n2) {
 }
 
 hipError_t launch_pc_mf(const void* echo, int dtype, float2* out, const PcMfArgs& a1, const PcMfArgs* a2,
-                        hipStream_t s) {
+                        int pc_rows, hipStream_t s) {
     if (a1.rows <= 0) return hipSuccess;
-    if (dtype == RSP_C64) return launch_pc_mf_t((const float2*)echo, out, a1, a2, s);
-    if (dtype == RSP_C32F16) return launch_pc_mf_t((const __half2*)echo, out, a1, a2, s);
+    if (dtype == RSP_C64) return launch_pc_mf_t((const float2*)echo, out, a1, a2, pc_rows, s);
+    if (dtype == RSP_C32F16) return launch_pc_mf_t((const __half2*)echo, out, a1, a2, pc_rows, s);
     return hipErrorInvalidValue;
 }
 

@@ -34,7 +34,7 @@ EXPORTS = ("rsp_version", "rsp_create", "rsp_destroy", "rsp_last_error", "rsp_se
            "rsp_pc_mtd_cfar_f64", "rsp_cfar_f64", "rsp_set_range_concat", "rsp_score_dev", "rsp_score_summary",
            "rsp_set_pc_prune", "rsp_set_lane_chunks", "rsp_pc_plan", "rsp_scr_dev", "rsp_inject_dev", "rsp_scr_gain",
            "rsp_cfar_plan", "rsp_legacy_record_bytes", "rsp_ingest_legacy_dev", "rsp_condense_dev", "rsp_cmap_dev",
-           "rsp_cmap_plan", "rsp_spec_width_dev", "rsp_track_dev")
+           "rsp_cmap_plan", "rsp_spec_width_dev", "rsp_track_dev", "rsp_set_pc_rows", "rsp_get_pc_rows")
 RSP_NKERNELS = 4
 KERNEL_NAMES = ("pc_kernel", "mtd_kernel", "cfar_r_kernel", "cfar_v_kernel")
 
@@ -244,6 +244,10 @@ def load_library(path=None):
     lib.rsp_set_pc_split.argtypes = [vp, i32]
     lib.rsp_set_pc_prune.restype = C.c_int
     lib.rsp_set_pc_prune.argtypes = [vp, i32]
+    lib.rsp_set_pc_rows.restype = C.c_int
+    lib.rsp_set_pc_rows.argtypes = [vp, i32]
+    lib.rsp_get_pc_rows.restype = C.c_int
+    lib.rsp_get_pc_rows.argtypes = [vp]
     lib.rsp_pc_plan.restype = C.c_int
     lib.rsp_pc_plan.argtypes = [vp, C.POINTER(rsp_pc_plan_t), i32]
     lib.rsp_cfar_plan.restype = C.c_int

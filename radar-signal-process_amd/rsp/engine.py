@@ -87,6 +87,16 @@ class Engine:
         unstored output slices (1, the default) or the generic instances (0) -- rsp_set_pc_prune."""
         capi.check(self.lib.rsp_set_pc_prune(self.ctx, int(enable)), self.ctx)
 
+    def set_pc_rows(self, n):
+        """Rows per workgroup of the 4096-point pulse-compression rows: 1, 2 or 4 (the spectrum
+        slice and twiddles are loaded once per workgroup), 0 = the library default -- rsp_set_pc_rows.
+        The stored values are bit-identical for every n."""
+        capi.check(self.lib.rsp_set_pc_rows(self.ctx, int(n)), self.ctx)
+
+    def pc_rows(self):
+        """Rows per workgroup the next launch of 4096-point rows runs (rsp_get_pc_rows)."""
+        return int(self.lib.rsp_get_pc_rows(self.ctx))
+
     def pc_plan(self):
         """The pulse-compression launches this context issues (rsp_pc_plan): a dict with
         specialised, fused, prune (the pruned instance's code, 0 = generic) and segs, one
