@@ -748,6 +748,77 @@ int rsp_spec_width_dev(rsp_ctx* ctx, const float* d_amp, const uint8_t* d_flag /
                        int64_t V, int64_t R, int64_t batch, const rsp_width_params* wp,
                        int32_t* d_span, int32_t* d_count, void* stream);
 
+/* ---- ordered-statistic CFAR: a second detector beside the GO/SO cell-averaging one --------- */
+/* executeCFAR.m with one substitution: the noise estimate of a reference window is its k-th
+ * smallest cell, not its mean.  A second target inside a reference window raises the mean and
+ * masks its neighbour; it moves the k-th smallest cell only when k cells or more are occupied.
+ * Everything else is rsp_cfar_dev's: the row band [M0 + 1, V - M0), the column segments (columns
+ * outside every segment are flagged 0), the rows of the zero_v_div band read as 0, the Doppler test
+ * on every band cell of every in-segment column (flagV), and with rFlag = 1 the range test on r-1,
+ * r, r+1 of every Doppler hit, confined to the hit's segment, the first maximum among the passing
+ * cells flagged (rFlag = 0: flag = flagV).
+ *
+ * For cell y of a line z whose valid part is [lo, hi) (a column's band rows; a band row's segment):
+ * L = [y-save-ref, y-save-1], Rt = [y+save+1, y+save+ref]; a side that leaves [lo, hi) is replaced
+ * by the other side (Function_CFAR1D_sub.m:30-39).
+ *   per side (union = 0, 1 <= k <= ref): a, b = the k-th smallest of z[L], z[Rt];
+ *                                        w = max(a, b) (method 0, GO) or min(a, b) (method 1, SO);
+ *   union    (union = 1, 1 <= k <= 2*ref, method ignored): w = the k-th smallest of the 2*ref
+ *                                        values of both sides as a multiset (at a one-sided cell the
+ *                                        valid side's values count twice).
+ * The cell passes iff z[y] >= fl32((float)T * w): one fp32 multiply, rounded to nearest.  T
+ * multiplies the order statistic itself; it is not divided by ref.
+ * Multiplication by a positive constant is monotone in IEEE arithmetic, so the test holds exactly
+ * when at least k window cells satisfy fl32(T * z_i) <= z[y]; with the side counts cl, cr (a missing
+ * side takes the other's count): GO cl >= k and cr >= k, SO cl >= k or cr >= k, union cl + cr >= k.
+ * The kernels count; they neither sort nor select, and the flags are bit-exact
+ * against a sorted restatement in fp32.  Inputs are magnitudes (finite, >= 0); a NaN leaves the
+ * cells whose windows contain it unspecified.
+ *
+ * d_rdm float32, d_flag and d_flagV (nullable) uint8 are [batch][V][ld] windows of R columns with
+ * the geometry of rsp_condense_dev / rsp_spec_width_dev.  Every byte of the window in d_flag (and
+ * d_flagV) is written; nothing outside the window is read or written.  cfar keeps its field
+ * meanings; the checks are rsp_cfar_dev's with the same codes, and further T finite and > 0 and k
+ * in range for its form (RSP_ERR_ARG); ref > RSP_OS_MAX_REF per side or V > RSP_OS_MAX_V:
+ * RSP_ERR_UNSUPPORTED (as is rsp_cfar_dev's own limit, a range guard + ref over 30 cells).  Arguments
+ * are checked before the context is looked at.  With rFlag = 1 and d_flagV == NULL the Doppler flags go to the context's scratch.
+ * No atomics; a flag byte is written once, by one thread: two runs give the same bytes, and a CPI
+ * alone gives the bytes it gives inside a batch.  Asynchronous on `stream`; works on any context,
+ * the CFAR-only kind included.  Timed under rsp_profile as RSP_K_OS_V / RSP_K_OS_R. */
+#define RSP_OS_MAX_REF 32
+#define RSP_OS_MAX_V 4096
+typedef struct {
+    int32_t kV, kR;          /* 1-based rank of the Doppler / range test */
+    int32_t unionV, unionR;  /* 0: per side, then methodV/methodR (0 GO, 1 SO); 1: both sides as one set */
+    int64_t ld;              /* row pitch in elements (0 = R), as rsp_width_params.ld */
+    int64_t cpi_stride;      /* elements between CPIs (0 = V * ld) */
+} rsp_os_params;
+
+int rsp_os_cfar_dev(rsp_ctx* ctx, const float* d_rdm, int64_t V, int64_t R, int64_t batch,
+                    const rsp_cfar_params* cfar, const rsp_os_params* os,
+                    uint8_t* d_flag, uint8_t* d_flagV /* nullable */, void* stream);
+
+/* The launches that call would make (read-only; nothing is launched, no buffer is touched), from the
+ * launchers' own host functions.  The Doppler kernel is one piece of code whose tile of
+ * 2^v_tile_log2 columns x V rows is sized by V alone (1..6 for V <= RSP_OS_MAX_V); the range stage
+ * is absent with rFlag = 0, where the Doppler kernel stores flag itself.  Returns what the call's
+ * validation would return. */
+enum { RSP_OS_R_NONE = 0,      /* rFlag == 0: the Doppler kernel writes flag = flagV */
+       RSP_OS_R_GATHER = 1 };  /* one workgroup per tile of a row; a tile without a Doppler hit in reach
+                                  stores zeros and leaves */
+typedef struct {
+    int32_t v_tile_log2;   /* log2 of the Doppler tile's columns */
+    int32_t v_pitch;       /* floats between the tile's columns in LDS */
+    int32_t r_stage;       /* RSP_OS_R_* */
+    int32_t r_tile;        /* columns per range workgroup (0 with RSP_OS_R_NONE) */
+    int32_t r_tiles;       /* range workgroups per row */
+    int32_t r_halo;        /* columns staged on each side of a range tile: guard + ref + 2 */
+    int32_t scratch_flagV; /* 1: flagV goes to the context's scratch (rFlag = 1, no d_flagV) */
+    int32_t reserved;      /* 0 */
+} rsp_os_plan_t;
+int rsp_os_cfar_plan(rsp_ctx* ctx, int64_t V, int64_t R, int64_t batch, const rsp_cfar_params* cfar,
+                     const rsp_os_params* os, int32_t with_flagV, rsp_os_plan_t* out);
+
 /* ---- tracking: the plots of successive CPIs joined into tracks ----------------------------- */
 /* DMX_SignalProcessing_main_xzr.m plots each frame's {rEst, vEst, eleAngleEst} against the frame
  * number and GPS truth (:530-601); the reference ships no stage that says which estimates of
@@ -1016,9 +1087,10 @@ int rsp_scr_gain(int32_t power, const double sum_simu[2], const double sum_clutt
  * kernel launches while profiling is enabled: enable = 1 brackets every launch, enable = N > 1
  * every N-th launch (sampling: each event pair costs the stream a few microseconds),
  * 0 stops.  Any call resets the counters.
- * Kernel ids: RSP_K_PC, RSP_K_MTD, RSP_K_CFAR_R, RSP_K_CFAR_V. */
-#define RSP_NKERNELS 4
-enum { RSP_K_PC = 0, RSP_K_MTD = 1, RSP_K_CFAR_R = 2, RSP_K_CFAR_V = 3 };
+ * Kernel ids: RSP_K_PC, RSP_K_MTD, RSP_K_CFAR_R, RSP_K_CFAR_V, and (an addition within ABI 5)
+ * RSP_K_OS_V, RSP_K_OS_R for rsp_os_cfar_dev's Doppler and range launches. */
+#define RSP_NKERNELS 6
+enum { RSP_K_PC = 0, RSP_K_MTD = 1, RSP_K_CFAR_R = 2, RSP_K_CFAR_V = 3, RSP_K_OS_V = 4, RSP_K_OS_R = 5 };
 int rsp_profile(rsp_ctx* ctx, int32_t enable);
 /* Waits for the recorded events; ms[k] = summed device time, launches[k] = launch count, for
  * k < n (n <= RSP_NKERNELS entries are written; pass the length of both arrays). */

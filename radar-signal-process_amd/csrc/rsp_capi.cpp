@@ -1459,6 +1459,112 @@ int rsp_cfar_dev(rsp_ctx* ctx, const float* d_rdm, int64_t V, int64_t R, int64_t
     return scratch_release(ctx, s);
 }
 
+// ------------------------------------------------------------------ ordered-statistic CFAR
+// rsp_os_cfar_dev's checks (no context needed: `ctx` only receives the message) and argument block.
+static int build_os(rsp_ctx* ctx, const char* who, int64_t V, int64_t R, int64_t batch, const rsp_cfar_params* cfar,
+                    const rsp_os_params* os, rsp::OsArgs* a) {
+    if (!cfar || !os) return fail(ctx, RSP_ERR_ARG, "%s: null %s", who, !cfar ? "cfar" : "os");
+    if (V < 1 || R < 1 || batch < 0)
+        return fail(ctx, RSP_ERR_ARG, "%s: bad shape V = %lld, R = %lld, batch = %lld", who, (long long)V, (long long)R,
+                    (long long)batch);
+    if (R > (1 << 24)) return fail(ctx, RSP_ERR_UNSUPPORTED, "%s: R = %lld over 2^24 not built", who, (long long)R);
+    rsp::CfarVArgs cv;
+    rsp::CfarRArgs cr;
+    int rc = build_cfar(ctx, cfar, V, R, &cv, &cr);
+    if (rc) return rc;
+    if (!std::isfinite(cfar->TV) || !(cfar->TV > 0) || !std::isfinite((float)cfar->TV))
+        return fail(ctx, RSP_ERR_ARG, "%s: TV = %g must be finite and > 0", who, cfar->TV);
+    if (cfar->rFlag && (!std::isfinite(cfar->TR) || !(cfar->TR > 0) || !std::isfinite((float)cfar->TR)))
+        return fail(ctx, RSP_ERR_ARG, "%s: TR = %g must be finite and > 0", who, cfar->TR);
+    if ((os->unionV != 0 && os->unionV != 1) || (os->unionR != 0 && os->unionR != 1))
+        return fail(ctx, RSP_ERR_ARG, "%s: union flags %d, %d must be 0 or 1", who, os->unionV, os->unionR);
+    if ((cfar->methodV != 0 && cfar->methodV != 1) || (cfar->rFlag && cfar->methodR != 0 && cfar->methodR != 1))
+        return fail(ctx, RSP_ERR_ARG, "%s: method %d, %d must be 0 (GO) or 1 (SO)", who, cfar->methodV, cfar->methodR);
+    if (cfar->refV > RSP_OS_MAX_REF || (cfar->rFlag && cfar->refR > RSP_OS_MAX_REF))
+        return fail(ctx, RSP_ERR_UNSUPPORTED, "%s: ref %d / %d over %d cells per side not built", who, cfar->refV,
+                    cfar->refR, RSP_OS_MAX_REF);
+    if (V > RSP_OS_MAX_V)
+        return fail(ctx, RSP_ERR_UNSUPPORTED, "%s: V = %lld over %d rows not built", who, (long long)V, RSP_OS_MAX_V);
+    const int kmaxV = os->unionV ? 2 * cfar->refV : cfar->refV, kmaxR = os->unionR ? 2 * cfar->refR : cfar->refR;
+    if (os->kV < 1 || os->kV > kmaxV)
+        return fail(ctx, RSP_ERR_ARG, "%s: kV = %d outside 1..%d (%s, refV = %d)", who, os->kV, kmaxV,
+                    os->unionV ? "union" : "per side", cfar->refV);
+    if (cfar->rFlag && (os->kR < 1 || os->kR > kmaxR))
+        return fail(ctx, RSP_ERR_ARG, "%s: kR = %d outside 1..%d (%s, refR = %d)", who, os->kR, kmaxR,
+                    os->unionR ? "union" : "per side", cfar->refR);
+    if (os->ld < 0 || os->cpi_stride < 0) return fail(ctx, RSP_ERR_ARG, "%s: negative row pitch / CPI stride", who);
+    const int64_t ld = os->ld ? os->ld : R, cs = os->cpi_stride ? os->cpi_stride : V * ld;
+    if (ld < R || cs < (V - 1) * ld + R)
+        return fail(ctx, RSP_ERR_ARG, "%s: row pitch %lld / CPI stride %lld too small for %lld x %lld", who,
+                    (long long)ld, (long long)cs, (long long)V, (long long)R);
+    std::memset(a, 0, sizeof(*a));
+    a->V = (int)V;
+    a->R = (int)R;
+    a->lo = cv.lo;
+    a->hi = cv.hi;
+    a->cz_lo = cv.cz_lo;
+    a->cz_hi = cv.cz_hi;
+    a->nseg = cv.nseg;
+    for (int s = 0; s < cv.nseg; ++s) {
+        a->seg_lo[s] = cv.seg_lo[s];
+        a->seg_hi[s] = cv.seg_hi[s];
+    }
+    a->rflag = cr.rflag;
+    a->v = rsp::OsTest{cfar->refV, cfar->saveV, os->kV, os->unionV ? rsp::kOsUnion : cfar->methodV, (float)cfar->TV};
+    a->r = rsp::OsTest{cfar->refR, cfar->saveR, os->kR, os->unionR ? rsp::kOsUnion : cfar->methodR, (float)cfar->TR};
+    a->ld = a->fv_ld = ld;
+    a->cs = a->fv_cs = cs;
+    return RSP_OK;
+}
+
+int rsp_os_cfar_dev(rsp_ctx* ctx, const float* d_rdm, int64_t V, int64_t R, int64_t batch,
+                    const rsp_cfar_params* cfar, const rsp_os_params* os, uint8_t* d_flag, uint8_t* d_flagV,
+                    void* stream) {
+    if (!d_rdm || !d_flag) return fail(ctx, RSP_ERR_ARG, "rsp_os_cfar_dev: null %s", !d_rdm ? "d_rdm" : "d_flag");
+    rsp::OsArgs a;
+    int rc = build_os(ctx, "rsp_os_cfar_dev", V, R, batch, cfar, os, &a);
+    if (rc) return rc;
+    if (!ctx) return fail(nullptr, RSP_ERR_ARG, "rsp_os_cfar_dev: null ctx");
+    if (batch == 0) return RSP_OK;
+    if (!set_device(ctx)) return fail(ctx, RSP_ERR_HIP, "hipSetDevice failed");
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t chunk = 65535;
+    const bool own_fv = a.rflag && !d_flagV;   // the Doppler flags go to the context's scratch, dense
+    if (own_fv) {
+        if ((rc = scratch_acquire(ctx, s))) return rc;
+        if ((rc = ensure(ctx, ctx->tmp_flagV, (size_t)(batch < chunk ? batch : chunk) * V * R))) return rc;
+        a.fv_ld = R;
+        a.fv_cs = V * R;
+    }
+    for (int64_t c0 = 0; c0 < batch; c0 += chunk) {
+        const int n = (int)(batch - c0 < chunk ? batch - c0 : chunk);
+        const float* rdm = d_rdm + c0 * a.cs;
+        uint8_t* fl = d_flag + c0 * a.cs;
+        uint8_t* fv = own_fv ? (uint8_t*)ctx->tmp_flagV.p : (d_flagV ? d_flagV + c0 * a.cs : nullptr);
+        HIP_TRY(ctx, timed(ctx, RSP_K_OS_V, s, [&] { return rsp::launch_os_v(rdm, a.rflag ? nullptr : fl, fv, n, a, s); }));
+        if (a.rflag) HIP_TRY(ctx, timed(ctx, RSP_K_OS_R, s, [&] { return rsp::launch_os_r(rdm, fv, fl, n, a, s); }));
+    }
+    return own_fv ? scratch_release(ctx, s) : RSP_OK;
+}
+
+int rsp_os_cfar_plan(rsp_ctx* ctx, int64_t V, int64_t R, int64_t batch, const rsp_cfar_params* cfar,
+                     const rsp_os_params* os, int32_t with_flagV, rsp_os_plan_t* out) {
+    if (!out) return fail(ctx, RSP_ERR_ARG, "rsp_os_cfar_plan: null out");
+    std::memset(out, 0, sizeof(*out));
+    rsp::OsArgs a;
+    int rc = build_os(ctx, "rsp_os_cfar_plan", V, R, batch, cfar, os, &a);
+    if (rc) return rc;
+    rsp::os_v_geometry(a.V, &out->v_tile_log2, &out->v_pitch);
+    out->r_stage = a.rflag ? RSP_OS_R_GATHER : RSP_OS_R_NONE;
+    if (a.rflag) {
+        out->r_tile = rsp::kOsRTile;
+        out->r_tiles = (a.R + rsp::kOsRTile - 1) / rsp::kOsRTile;
+        out->r_halo = a.r.save + a.r.ref + 2;
+        out->scratch_flagV = with_flagV ? 0 : 1;
+    }
+    return RSP_OK;
+}
+
 int rsp_cfar_plan(rsp_ctx* ctx, int64_t V, int64_t R, int64_t batch, const rsp_cfar_params* cfar, int32_t fused,
                   int32_t with_rdm, rsp_cfar_plan_t* out) {
     if (!ctx) return fail(nullptr, RSP_ERR_ARG, "rsp_cfar_plan: null ctx");

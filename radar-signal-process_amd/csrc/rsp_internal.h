@@ -231,6 +231,37 @@ size_t width_lds_bytes(int V, int interp);
 hipError_t launch_width(const float* amp, const uint8_t* flag, int batch, const WidthArgs& a, int32_t* span,
                         int32_t* count, hipStream_t st);
 
+// Ordered-statistic CFAR (rsp_oscfar.hip): one 1-D test (rank k of a window of ref cells beyond save
+// guard cells, threshold T) per stage, and the planes' geometry.
+enum { kOsGo = 0, kOsSo = 1, kOsUnion = 2 };
+struct OsTest {
+    int ref, save, k, form;   // form: kOsGo / kOsSo (per side), kOsUnion (both sides as one set)
+    float T;
+};
+struct OsArgs {
+    int V, R;
+    int lo, hi;            // band rows
+    int cz_lo, cz_hi;      // rows read as zero
+    int nseg;
+    int seg_lo[RSP_MAX_SEG], seg_hi[RSP_MAX_SEG];
+    int rflag;
+    OsTest v, r;
+    int64_t ld, cs;        // row pitch and CPI stride of the RDM and flag planes, in elements
+    int64_t fv_ld, fv_cs;  // those of the flagV plane (the caller's window, or the dense scratch)
+};
+constexpr int kOsRTile = 1024;   // columns per range workgroup
+// The Doppler tile of a V-row plane: log2 of its columns and the LDS floats between them.
+void os_v_geometry(int V, int* lw, int* pitch);
+size_t os_v_lds_bytes(int V);
+// Dynamic LDS of a range workgroup: the tile and a halo of save + ref + 2 columns on each side,
+// 10 bytes per column.
+size_t os_r_lds_bytes(const OsTest& r);
+// flagV (and, with a.rflag == 0, flag; either may be null) of batch CPIs (at most 65535).
+hipError_t launch_os_v(const float* rdm, uint8_t* flag, uint8_t* flagV, int batch, const OsArgs& a, hipStream_t st);
+// flag from flagV (a.rflag == 1).
+hipError_t launch_os_r(const float* rdm, const uint8_t* flagV, uint8_t* flag, int batch, const OsArgs& a,
+                       hipStream_t st);
+
 // Tracking (rsp_track.hip): rsp_track_params with the shape and the gate weights.
 struct TrackArgs {
     int T, H;              // max_tracks, max_hits

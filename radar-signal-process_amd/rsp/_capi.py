@@ -34,9 +34,10 @@ EXPORTS = ("rsp_version", "rsp_create", "rsp_destroy", "rsp_last_error", "rsp_se
            "rsp_pc_mtd_cfar_f64", "rsp_cfar_f64", "rsp_set_range_concat", "rsp_score_dev", "rsp_score_summary",
            "rsp_set_pc_prune", "rsp_set_lane_chunks", "rsp_pc_plan", "rsp_scr_dev", "rsp_inject_dev", "rsp_scr_gain",
            "rsp_cfar_plan", "rsp_legacy_record_bytes", "rsp_ingest_legacy_dev", "rsp_condense_dev", "rsp_cmap_dev",
-           "rsp_cmap_plan", "rsp_spec_width_dev", "rsp_track_dev", "rsp_set_pc_rows", "rsp_get_pc_rows")
-RSP_NKERNELS = 4
-KERNEL_NAMES = ("pc_kernel", "mtd_kernel", "cfar_r_kernel", "cfar_v_kernel")
+           "rsp_cmap_plan", "rsp_spec_width_dev", "rsp_track_dev", "rsp_set_pc_rows", "rsp_get_pc_rows",
+           "rsp_os_cfar_dev", "rsp_os_cfar_plan")
+RSP_NKERNELS = 6
+KERNEL_NAMES = ("pc_kernel", "mtd_kernel", "cfar_r_kernel", "cfar_v_kernel", "os_v_kernel", "os_r_kernel")
 
 
 class RspError(RuntimeError):
@@ -121,6 +122,21 @@ RSP_WIDTH_MIN_V, RSP_WIDTH_MAX_V = 4, 2048
 class rsp_width_params(C.Structure):
     _fields_ = [("amp_constr", C.c_double), ("interp", C.c_int32), ("shift", C.c_int32), ("ld", C.c_int64),
                 ("cpi_stride", C.c_int64)]
+
+
+RSP_OS_MAX_REF, RSP_OS_MAX_V = 32, 4096
+# rsp_os_plan_t.r_stage
+RSP_OS_R_NONE, RSP_OS_R_GATHER = 0, 1
+
+
+class rsp_os_params(C.Structure):
+    _fields_ = [("kV", C.c_int32), ("kR", C.c_int32), ("unionV", C.c_int32), ("unionR", C.c_int32),
+                ("ld", C.c_int64), ("cpi_stride", C.c_int64)]
+
+
+class rsp_os_plan_t(C.Structure):
+    _fields_ = [("v_tile_log2", C.c_int32), ("v_pitch", C.c_int32), ("r_stage", C.c_int32), ("r_tile", C.c_int32),
+                ("r_tiles", C.c_int32), ("r_halo", C.c_int32), ("scratch_flagV", C.c_int32), ("reserved", C.c_int32)]
 
 
 RSP_TRACK_MAX_TRACKS = 1024
@@ -279,6 +295,12 @@ def load_library(path=None):
     lib.rsp_cmap_plan.argtypes = [vp, i64, i64, C.POINTER(rsp_cmap_params), C.POINTER(rsp_cmap_plan_t)]
     lib.rsp_spec_width_dev.restype = C.c_int
     lib.rsp_spec_width_dev.argtypes = [vp, vp, vp, i64, i64, i64, C.POINTER(rsp_width_params), vp, vp, vp]
+    lib.rsp_os_cfar_dev.restype = C.c_int
+    lib.rsp_os_cfar_dev.argtypes = [vp, vp, i64, i64, i64, C.POINTER(rsp_cfar_params), C.POINTER(rsp_os_params), vp, vp,
+                                    vp]
+    lib.rsp_os_cfar_plan.restype = C.c_int
+    lib.rsp_os_cfar_plan.argtypes = [vp, i64, i64, i64, C.POINTER(rsp_cfar_params), C.POINTER(rsp_os_params), i32,
+                                     C.POINTER(rsp_os_plan_t)]
     lib.rsp_track_dev.restype = C.c_int
     lib.rsp_track_dev.argtypes = [vp, vp, vp, i64, i64, C.POINTER(rsp_track_params), vp, vp, i32, vp, vp, vp, vp, vp,
                                   vp, vp, vp]

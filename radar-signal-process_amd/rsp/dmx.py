@@ -69,6 +69,7 @@ class DmxFrameProcessor:
         self._width = None
         self._tracker = None
         self._track_opts = None
+        self._os = None
 
     def close(self):
         self.eng.close()
@@ -120,7 +121,22 @@ class DmxFrameProcessor:
             out[(part, fk, "tracks")] = self._tracker.update_dev(est, count, slot=slot)
         return out
 
-    def process_dev(self, echo, beamPosNum, with_flagV=True, max_hits=4096, condense=None, width=None, track=None):
+    def _detector_options(self, detector):
+        """detector=dict(...) as (cfar, k, union): the preset's CFAR with T replaced when given."""
+        import dataclasses
+        detector = dict(detector)
+        if "k" not in detector:
+            raise TypeError("process_dev: detector needs k=(kV, kR)")
+        k = tuple(int(x) for x in detector.pop("k"))
+        union = tuple(bool(x) for x in detector.pop("union", (False, False)))
+        T = detector.pop("T", None)
+        if detector:
+            raise TypeError("process_dev: detector takes k, union and T, not %s" % sorted(detector))
+        cfar = self.cfar if T is None else dataclasses.replace(self.cfar, TV=float(T[0]), TR=float(T[1]))
+        return cfar, k, union
+
+    def process_dev(self, echo, beamPosNum, with_flagV=True, max_hits=4096, condense=None, width=None, track=None,
+                    detector=None):
         """echo: complex64 [batch][2][P][R] (left, right) on the device.  Returns a dict of
         device outputs: the planes (sum, diff, flag, flagV) and, per part ('short', 'long') and
         flag kind ('flag', 'flagV'), (est, cells, count) as Measure.measure_dev gives them.
@@ -148,8 +164,16 @@ class DmxFrameProcessor:
         consecutive in time, and reset_tracks() clears it.  A call whose options differ from the
         previous call's starts a new Tracker.  Without condense every hit of a target starts its
         own track (a target lights several cells): track the plots, not the hits.  track=None
-        leaves every other output as it is."""
+        leaves every other output as it is.
+
+        detector = dict(k=(kV, kR), union=(False, False), T=(TV, TR)): the chain runs pulse
+        compression and the MTD only, and flag / flagV come from one ordered-statistic CFAR call
+        (OsCfar.detect_dev) over the whole sum plane with the preset's window, M0 and segments (T
+        defaults to the preset's).  The measurement, condense, width and track run on those flags
+        unchanged; flagV is always computed.  detector=None leaves the chain's own CFAR."""
         import torch
+        if detector is not None:
+            detector = self._detector_options(detector)
         if track is not None:
             track = self._track_options(track)
         if width is not None:
@@ -163,8 +187,15 @@ class DmxFrameProcessor:
         dev = self.device
         out = {k: torch.empty(shp, dtype=t, device=dev) for k, t in
                (("sum", torch.float32), ("diff", torch.float32), ("flag", torch.uint8), ("flagV", torch.uint8))}
-        self.eng.run_dev(echo, rdm=out["sum"], diff=out["diff"], flag=out["flag"],
-                         flagV=out["flagV"] if with_flagV else None, cfar=self.cfar)
+        if detector is None:
+            self.eng.run_dev(echo, rdm=out["sum"], diff=out["diff"], flag=out["flag"],
+                             flagV=out["flagV"] if with_flagV else None, cfar=self.cfar)
+        else:
+            from .oscfar import OsCfar
+            if self._os is None:
+                self._os = OsCfar(engine=self.eng)
+            self.eng.run_dev(echo, rdm=out["sum"], diff=out["diff"], cfar=None)
+            self._os.detect_dev(out["sum"], detector[0], detector[1], detector[2], flag=out["flag"], flagV=out["flagV"])
         rS, rL, vS, dR, dV = self.scales
         o = self.o
         k_value = float(self.kValues[self.freInd, int(beamPosNum)])
@@ -221,7 +252,7 @@ class DmxFrameProcessor:
         return out
 
     def process_records_dev(self, d_stream, nbytes, nframes, with_flagV=True, max_hits=4096, condense=None,
-                            width=None, track=None):
+                            width=None, track=None, detector=None):
         """:307-310 + process_dev from the record bytes: d_stream holds nframes * P consecutive
         legacy records (uint8 on the device, 4-byte aligned; the layout assumed for this waveform,
         see the module docstring), decoded into [nframes][2][P][R] without leaving HBM.  As the main
@@ -232,8 +263,8 @@ class DmxFrameProcessor:
         process_dev measures a batch at one beam position, so the frames are processed in runs of
         consecutive frames that share beamPosNum.  Returns a list with one dict per run:
         process_dev's outputs for the run's frames plus 'frames' (first, end), 'beamPosNum',
-        'frameInd' (int64 [n]) and 'angleCode' (float64 [n][P], host).  condense, width, track: as
-        process_dev's; the runs at different beamPosNum feed the same track slots, because the frames
+        'frameInd' (int64 [n]) and 'angleCode' (float64 [n][P], host).  condense, width, track, detector:
+        as process_dev's; the runs at different beamPosNum feed the same track slots, because the frames
         are consecutive in time and eleAngleEst is absolute."""
         from . import _capi as capi
         from .ingest import LegacyIngest
@@ -256,7 +287,7 @@ class DmxFrameProcessor:
         for b in range(1, F + 1):
             if b == F or bpn[b] != bpn[a]:
                 out = self.process_dev(echo[a:b], int(bpn[a]), with_flagV=with_flagV, max_hits=max_hits,
-                                       condense=condense, width=width, track=track)
+                                       condense=condense, width=width, track=track, detector=detector)
                 out.update(frames=(a, b), beamPosNum=int(bpn[a]), frameInd=frame_ind[a:b], angleCode=code[a:b])
                 runs.append(out)
                 a = b

@@ -21,6 +21,7 @@ threshold loop (:40), with the reference's names and argument meaning:
   * scr_sweep(engine, clutter_dev, plan, SCR_values, cfar, seg): the Pd-versus-SCR loop: for
     each SCR the plan's targets are injected into the clutter on the device (rsp.inject), the
     chain and the CFAR run, and the flags are scored against the plan's truth cells.
+    Both sweeps take detector=, a callable in place of the chain's CFAR (rsp.oscfar.detector).
 
 Quirks of the reference kept as they are: `for i=1:length(cfarFlag_all)` is the largest
 dimension of the 3-D array (here the loop runs over the batch, the first dimension), and
@@ -230,13 +231,15 @@ def summary(rec, truth_idx, V, R, params, lib=None):
                 n_multi_peak=out.n_multi_peak)
 
 
-def sweep(engine, echo_dev, truth_idx, T_values, cfar, params=None, on_step=None):
+def sweep(engine, echo_dev, truth_idx, T_values, cfar, params=None, on_step=None, detector=None):
     """The `for T=[...]` loop of main_cfar.m:40-58 on a device-resident echo batch: PC + MTD
     run once (the RDM does not depend on T); for each T the CFAR runs with TR = TV = T
     (T_CFAR_R = T_CFAR_V = T_CFAR, :47-53) through Engine.cfar_dev and the flags are scored
     where they are.  Only the batch x 8 records cross PCIe.  params: default the reference's
     box sizes with v_lim, r_lim = the RDM's own size.  on_step(T, flag, rdm, rec), if given,
-    sees each step's device tensors (the same rdm object every time).  Returns
+    sees each step's device tensors (the same rdm object every time).  detector, if given, is a
+    callable (rdm, flag, cfar) that fills flag from rdm with the step's cfar in place of
+    Engine.cfar_dev (rsp.oscfar.detector: the ordered-statistic CFAR).  Returns
     [dict(T=T, **summary)] in the order of T_values."""
     import torch
     spec = engine.spec
@@ -252,7 +255,10 @@ def sweep(engine, echo_dev, truth_idx, T_values, cfar, params=None, on_step=None
     out = []
     for T in T_values:
         c = dataclasses.replace(cfar, TR=float(T), TV=float(T))
-        engine.cfar_dev(rdm, flag, cfar=c)
+        if detector is None:
+            engine.cfar_dev(rdm, flag, cfar=c)
+        else:
+            detector(rdm, flag, c)
         rec = scorer.score_dev(flag, rdm, truth_idx, params)
         if on_step is not None:
             on_step(T, flag, rdm, rec)
@@ -260,14 +266,17 @@ def sweep(engine, echo_dev, truth_idx, T_values, cfar, params=None, on_step=None
     return out
 
 
-def scr_sweep(engine, clutter_dev, plan, SCR_values, cfar, seg=0, params=None, on_step=None, power=None):  # noqa: N803
+def scr_sweep(engine, clutter_dev, plan, SCR_values, cfar, seg=0, params=None, on_step=None, power=None,  # noqa: N803
+              detector=None):
     """Detection scores over a sweep of signal-to-clutter ratios, everything in device memory:
     for each SCR [dB] the plan's point targets (rsp.inject.target_plan, one per CPI) are injected
     into clutter_dev ([K][P][R] complex64, K <= plan.batch) at that SCR into one reused buffer
     (rsp_inject_dev), the chain runs with `cfar` (Engine.run_dev) and the flags are scored against
     plan.truth_cells(spec, seg), the target in pulse-compression segment `seg`.  Only the batch x 8
     records cross PCIe.  params: default the reference's box sizes with v_lim, r_lim = the RDM's
-    own size.  on_step(SCR, flag, rdm, rec), if given, sees each step's device tensors.  Returns
+    own size.  on_step(SCR, flag, rdm, rec), if given, sees each step's device tensors.  detector,
+    if given, is a callable (rdm, flag, cfar): the chain then runs without its CFAR
+    (run_dev(echo, rdm=rdm)) and the detector fills flag from rdm.  Returns
     [dict(SCR=SCR, **summary)] in the order of SCR_values."""
     import torch
     from . import inject
@@ -286,7 +295,11 @@ def scr_sweep(engine, clutter_dev, plan, SCR_values, cfar, seg=0, params=None, o
     out = []
     for scr in SCR_values:
         inj.inject_dev(clutter_dev, plan, float(scr), out=echo, power=inject.ABS2 if power is None else power)
-        engine.run_dev(echo, rdm=rdm, flag=flag, cfar=cfar)
+        if detector is None:
+            engine.run_dev(echo, rdm=rdm, flag=flag, cfar=cfar)
+        else:
+            engine.run_dev(echo, rdm=rdm)
+            detector(rdm, flag, cfar)
         rec = scorer.score_dev(flag, rdm, truth, params)
         if on_step is not None:
             on_step(scr, flag, rdm, rec)
