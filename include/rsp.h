@@ -542,7 +542,9 @@ int rsp_ingest_legacy_dev(rsp_ctx* ctx, const uint8_t* d_stream, int64_t nbytes,
  * d_count[cpi*2] = hits in the CPI (only the first max_hits are written), d_count[cpi*2+1] =
  * hits the reference stops at with an index error (a hit too close to an edge for the
  * re-anchoring at :24-32 / :51-59); their estimates are NaN.  With mp->ld > R the three
- * planes are R-column windows of rows ld elements apart. */
+ * planes are R-column windows of rows ld elements apart.
+ * A flag byte of any nonzero value is a hit.  Slots of d_est / d_cells at or past
+ * min(d_count[cpi*2], max_hits) are left untouched. */
 typedef struct {
     int32_t extra_dots;      /* extraDots (2), 1..4: 2*extraDots+1 cells per spline */
     int32_t r_interp;        /* rInterpTimes (8), 1..64 */
@@ -566,6 +568,31 @@ int rsp_motion_measure_dev(rsp_ctx* ctx, const float* d_sum, const float* d_diff
                            int64_t V, int64_t R, int64_t batch, const rsp_measure_params* mp,
                            const double* d_r_scale, const double* d_v_scale, int64_t max_hits,
                            double* d_est, int32_t* d_cells /* nullable */, int32_t* d_count, void* stream);
+
+/* The hit-list geometry a call would take (read-only; an addition within ABI 5): nothing is
+ * launched and no buffer is touched.  d_flag is looked at for its alignment only (it is never
+ * dereferenced; NULL is refused as the call refuses it).  Returns what rsp_motion_measure_dev's own
+ * validation of V, R, batch and mp would return; ctx may be NULL (it only receives the message).
+ * One workgroup of 1024 threads lists a CPI's hits.  A thread owns `cw` adjacent columns of one
+ * of `slices` row slices; a pass covers groups * cw columns and `passes` passes cover R.  Slice s
+ * owns rows min(V, s*rows) .. min(V, (s+1)*rows), and keeps one bit per q of its rows to find
+ * its hits again.  wide (16-byte flag loads, cw = 16) needs R % 16 == 0, R >= 256, and the flag
+ * address, the row pitch and the CPI stride all multiples of 16; everything else reads bytes
+ * (cw = 1).  The two paths give the same bytes.
+ * The same geometry, from the peak plane's address and the window's V, R, ld and cpi_stride,
+ * governs the list rsp_condense_dev makes from its peak plane (the order of d_plots). */
+typedef struct {
+    int32_t wide;     /* 1: 16-byte flag loads */
+    int32_t cw;       /* columns per thread: 16 or 1 */
+    int32_t groups;   /* column groups per pass: a power of two, 16 (wide) / 64 (bytes) .. 1024 */
+    int32_t slices;   /* row slices: 1024 / groups */
+    int32_t rows;     /* rows per slice: ceil(V / slices) (of a band's rows where bands > 1) */
+    int32_t q;        /* rows per bit of a thread's row mask: ceil(rows / 64) */
+    int32_t passes;   /* ceil(R / (groups * cw)) */
+    int32_t bands;    /* workgroups per CPI: 1 in the shipped library */
+} rsp_measure_plan_t;
+int rsp_measure_plan(rsp_ctx* ctx, const uint8_t* d_flag, int64_t V, int64_t R, int64_t batch,
+                     const rsp_measure_params* mp, rsp_measure_plan_t* out);
 
 /* ---- plot condensation: one peak cell per cluster of CFAR hits -------------------------- */
 /* The reference scatters one estimate per CFAR hit (DMX_SignalProcessing_main_xzr.m:530-558); the

@@ -9,6 +9,7 @@
 #include <mutex>
 
 #include "../../include/rsp.h"
+#include "rsp_measure_math.h"
 
 namespace rsp {
 
@@ -162,12 +163,7 @@ struct MtdArgs {
 
 
 // Raw-data ingest (rsp_ingest.hip): one frame of uniform DDC PRT records.
-// motionParaMeasure.m's scalar arguments (rsp_measure_params, rsp_measure.hip).
-struct MeasureArgs {
-    int extra_dots, r_interp, v_interp, mtd0_num, beam_pos_num;
-    double delta_r, delta_v, k_value, beam_angle_step, ele_comp, ele_sys_err;
-    int64_t ld, cs;   // row pitch and CPI stride of the planes, in elements
-};
+// MeasureArgs (motionParaMeasure.m's scalar arguments): rsp_measure_math.h.
 // Workgroups per CPI for the hit lists (1: hits_kernel; > 1: the banded path, which needs
 // batch * nb * R int32 of scratch in band_cnt).
 int measure_bands(int V, int batch);

@@ -19,9 +19,10 @@
 //                   measuring them inside the CPI's workgroup) keeps the per-hit dependent
 //                   loads and fp64 work off the flag scan's critical path.
 // The measurement is fp64 with contraction off, in the same operation order as the oracle
-// (oracle/measure_ref.py), so the estimates are bit-identical to it.  The flag scan is the
-// HBM traffic (V*R bytes per CPI, read once from HBM, once more from cache for the rows with
-// hits); the spline work is a few thousand fp64 operations per hit.
+// (oracle/measure_ref.py), so the estimates are bit-identical to it; its arithmetic is in
+// rsp_measure_math.h (shared with a host program), the launch geometry in rsp_measplan.h.
+// The flag scan is the HBM traffic (V*R bytes per CPI, read once from HBM, once more from
+// cache for the rows with hits); the spline work is a few thousand fp64 operations per hit.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -29,123 +30,20 @@
 
 #include "../../include/rsp.h"
 #include "rsp_internal.h"
+#include "rsp_measplan.h"
+#include "rsp_measure_math.h"
 
 namespace rsp {
 
 namespace {
 
-constexpr int kThreads = 1024;
+constexpr int kThreads = kMeasThreads;
 
-// MATLAB's a:d:b element i of n (colon: first half from a, second half from b).
-__device__ __forceinline__ double colon_at(double a, double d, double b, int i, int n) {
-#pragma clang fp contract(off)
-    return 2 * i < n ? a + (double)i * d : b - (double)(n - 1 - i) * d;
-}
-
-// Second derivatives of the not-a-knot cubic spline through y[0..N) at unit-spaced knots
-// (oracle/measure_ref.py spline_m).
-template <int N>
-__device__ __forceinline__ void spline_m(const double (&y)[N], double (&m)[N]) {
-#pragma clang fp contract(off)
-    if constexpr (N == 3) {
-        const double c = y[2] - 2.0 * y[1] + y[0];
-        m[0] = c;
-        m[1] = c;
-        m[2] = c;
-    } else {
-        double d[N - 2];
-#pragma unroll
-        for (int i = 1; i < N - 1; ++i) d[i - 1] = 6.0 * (y[i + 1] - 2.0 * y[i] + y[i - 1]);
-        m[1] = d[0] / 6.0;
-        m[N - 2] = d[N - 3] / 6.0;
-        constexpr int K = N - 4;
-        if constexpr (K > 0) {
-            double rhs[K], c[K], g[K];
-#pragma unroll
-            for (int i = 0; i < K; ++i) rhs[i] = d[i + 1];
-            rhs[0] -= m[1];
-            rhs[K - 1] -= m[N - 2];
-            c[0] = 1.0 / 4.0;
-            g[0] = rhs[0] / 4.0;
-#pragma unroll
-            for (int i = 1; i < K; ++i) {
-                const double den = 4.0 - c[i - 1];
-                c[i] = 1.0 / den;
-                g[i] = (rhs[i] - g[i - 1]) / den;
-            }
-            m[2 + K - 1] = g[K - 1];
-#pragma unroll
-            for (int i = K - 2; i >= 0; --i) m[2 + i] = g[i] - c[i] * m[2 + i + 1];
-        }
-        m[0] = 2.0 * m[1] - m[2];
-        m[N - 1] = 2.0 * m[N - 2] - m[N - 3];
-    }
-}
-
-// The 1-based cell of the first maximum of the spline through y on cells first..first+N-1,
-// sampled at first : 1/interp : first+N-1 (motionParaMeasure.m:36-42, :63-69).  Each interval
-// j is evaluated in Horner form y_j + u*(b_j + u*(c_j + u*d_j)) (oracle/measure_ref.py
-// spline_eval); the samples are walked interval by interval (their abscissae are increasing),
-// so every coefficient stays in a register.
-template <int N>
-__device__ double refine(const double (&y)[N], int first, int interp) {
-#pragma clang fp contract(off)
-    double m[N];
-    spline_m<N>(y, m);
-    double cb[N - 1], cc[N - 1], cd[N - 1];
-#pragma unroll
-    for (int j = 0; j < N - 1; ++j) {
-        cb[j] = (y[j + 1] - y[j]) - (2.0 * m[j] + m[j + 1]) / 6.0;
-        cc[j] = m[j] / 2.0;
-        cd[j] = (m[j + 1] - m[j]) / 6.0;
-    }
-    const double a = (double)first, b = (double)(first + N - 1);
-    const double d = 1.0 / (double)interp;
-    const int n = (int)floor((b - a) / d + 1e-10) + 1;
-    double best = -INFINITY, qbest = a;
-    int i = 0;
-#pragma unroll
-    for (int j = 0; j < N - 1; ++j) {
-        for (; i < n; ++i) {
-            const double q = colon_at(a, d, b, i, n);
-            const double t = q - a;
-            int jj = (int)floor(t);
-            jj = jj < 0 ? 0 : (jj > N - 2 ? N - 2 : jj);
-            if (jj > j) break;
-            const double u = t - (double)j;
-            const double v = y[j] + u * (cb[j] + u * (cc[j] + u * cd[j]));
-            if (v > best) {
-                best = v;
-                qbest = q;
-            }
-        }
-    }
-    return qbest;
-}
-
-// motionParaMeasure.m:22-33 / :49-60: the first of the 2e+1 cells around `center` (1-based),
-// moved up to lo or down to hi by anchoring on a member of the set; false where the
-// reference's find() comes back empty or the cells leave 1..size (a MATLAB error there).
-__device__ __forceinline__ bool fix_cells(int center, int e, int lo, int hi, int size, int* first) {
-    int f = center - e;
-    if (f < lo) {
-        if (lo > f + 2 * e) return false;
-        f = lo;
-    }
-    if (f + 2 * e > hi) {
-        if (hi < f) return false;
-        f = hi - 2 * e;
-    }
-    if (f < 1 || f + 2 * e > size) return false;
-    *first = f;
-    return true;
-}
-
+// One hit: the cells re-anchored, its values loaded, the arithmetic of rsp_measure_math.h.
 template <int E>
 __device__ void measure_hit(const float* __restrict__ sum, const float* __restrict__ diff, int V, int R, int v0,
                             int r0, const MeasureArgs& a, const double* __restrict__ r_scale,
                             const double* __restrict__ v_scale, double* est, bool* bad) {
-#pragma clang fp contract(off)
     constexpr int N = 2 * E + 1;
     const int v1 = v0 + 1, r1 = r0 + 1;
     int rf, vf;
@@ -166,23 +64,7 @@ __device__ void measure_hit(const float* __restrict__ sum, const float* __restri
     }
     const float s_hit = sum[(size_t)v0 * a.ld + r0], d_hit = diff[(size_t)v0 * a.ld + r0];
     const double rs = r_scale[r0];
-    double y[N];
-#pragma unroll
-    for (int k = 0; k < N; ++k) y[k] = (double)fr[k];
-    const double r_max = refine<N>(y, rf, a.r_interp);
-#pragma unroll
-    for (int k = 0; k < N; ++k) y[k] = (double)fvv[k];
-    const double v_max = refine<N>(y, vf, a.v_interp);
-    const double fv = trunc(v_max);
-    const int kv = (int)fv - vf;   // 0..N-1: v_max lies in [vf, vf+N-1]
-    double vsel = vs[0];
-#pragma unroll
-    for (int k = 1; k < N; ++k)
-        if (kv == k) vsel = vs[k];
-    est[0] = rs + (r_max - (double)r1) * a.delta_r;                                  // :43
-    est[1] = vsel - (v_max - fv) * a.delta_v;                                        // :70
-    const double ratio = (double)d_hit / (double)s_hit;                              // :78
-    est[2] = (double)a.beam_pos_num * a.beam_angle_step + 2.5 - ratio * a.k_value + a.ele_comp + a.ele_sys_err;   // :79
+    measure_values<E>(fr, fvv, vs, s_hit, d_hit, rs, r1, rf, vf, a, est);
     *bad = false;
 }
 
@@ -520,12 +402,9 @@ template <int E>
 hipError_t launch_e(const float* sum, const float* diff, const uint8_t* flag, int V, int R, int batch,
                     const MeasureArgs& a, const double* r_scale, const double* v_scale, int64_t max_hits,
                     double* est, int32_t* cells, int32_t* count, int32_t* band_cnt, int nb, hipStream_t st) {
-    const bool wide = R % 16 == 0 && R >= 16 * 16 && a.ld % 16 == 0 && a.cs % 16 == 0 && ((uintptr_t)flag & 15) == 0;
-    // column groups per pass: a power of two covering the columns (16-byte groups: at least 16,
-    // one 256-byte row segment per 16 lanes; bytes: at least 64), at most 1024
-    int G = wide ? 16 : 64;
-    const int groups = wide ? R / 16 : R;
-    while (G < groups && G < kThreads) G <<= 1;
+    const MeasPlan pl = meas_plan(V, R, a.ld, a.cs, (uintptr_t)flag, nb);   // rsp_measplan.h
+    const bool wide = pl.wide;
+    const int G = pl.G;
     if (nb > 1) {   // banded: nb workgroups per CPI
         const int Vb = (V + nb - 1) / nb;
         const unsigned grid = (unsigned)((int64_t)batch * nb);
@@ -584,10 +463,9 @@ hipError_t launch_hit_list(const uint8_t* flag, int V, int R, int batch, int64_t
     if (batch <= 0) return hipSuccess;
     // launch_e's choice of instance for one workgroup per CPI; E and mtd0_num only classify the
     // hits past max_hits, which no caller of the list reads
-    const bool wide = R % 16 == 0 && R >= 16 * 16 && ld % 16 == 0 && cs % 16 == 0 && ((uintptr_t)flag & 15) == 0;
-    int G = wide ? 16 : 64;
-    const int groups = wide ? R / 16 : R;
-    while (G < groups && G < kThreads) G <<= 1;
+    const MeasPlan pl = meas_plan(V, R, ld, cs, (uintptr_t)flag, 1);
+    const bool wide = pl.wide;
+    const int G = pl.G;
     double* est = reinterpret_cast<double*>(list);
     if (wide)
         hipLaunchKernelGGL((hits_kernel<1, 16>), dim3(batch), dim3(kThreads), 0, st, flag, V, R, G, ld, cs, 0, max_hits,

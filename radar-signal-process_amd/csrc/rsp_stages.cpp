@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "rsp_ctx.h"
+#include "rsp_measplan.h"
 
 using rsp::make_window;
 using rsp::scratch_acquire;
@@ -21,6 +22,50 @@ using rsp::scratch_release;
 using rsp::upload;
 
 // ------------------------------------------------------------------ post-detection measurement
+// Everything rsp_motion_measure_dev checks about the shape and the parameters, for it and for
+// rsp_measure_plan; fills the resolved pitches.
+static int measure_check(rsp_ctx* ctx, const char* who, int64_t V, int64_t R, int64_t batch,
+                         const rsp_measure_params* mp, int64_t* ld_out, int64_t* cs_out) {
+    const int64_t n = 2 * (int64_t)mp->extra_dots + 1;
+    if (mp->extra_dots < 1 || mp->extra_dots > 4)
+        return fail(ctx, RSP_ERR_UNSUPPORTED, "%s: extra_dots %d outside 1..4", who, mp->extra_dots);
+    if (mp->r_interp < 1 || mp->r_interp > 64 || mp->v_interp < 1 || mp->v_interp > 64)
+        return fail(ctx, RSP_ERR_ARG, "%s: interpolation factors %d, %d outside 1..64", who, mp->r_interp,
+                    mp->v_interp);
+    if (V < 1 || R < 1 || V > (1 << 20) || R > (1 << 20) || V * R > (int64_t)1 << 31 || batch > 0x7fffffff)
+        return fail(ctx, RSP_ERR_ARG, "%s: bad shape %lld x %lld x %lld", who, (long long)batch, (long long)V,
+                    (long long)R);
+    if (R < n || mp->mtd0_num < 0 || V - 2 * (int64_t)mp->mtd0_num - 1 < n)
+        return fail(ctx, RSP_ERR_ARG, "%s: %lld range bins / %lld unzeroed rows are fewer than 2*extraDots+1", who,
+                    (long long)R, (long long)(V - 2 * (int64_t)mp->mtd0_num - 1));
+    const int64_t ld = mp->ld ? mp->ld : R, cs = mp->cpi_stride ? mp->cpi_stride : V * ld;
+    if (ld < R || cs < (V - 1) * ld + R)
+        return fail(ctx, RSP_ERR_ARG, "%s: row pitch %lld / CPI stride %lld too small for %lld x %lld", who,
+                    (long long)ld, (long long)cs, (long long)V, (long long)R);
+    *ld_out = ld;
+    *cs_out = cs;
+    return RSP_OK;
+}
+
+int rsp_measure_plan(rsp_ctx* ctx, const uint8_t* d_flag, int64_t V, int64_t R, int64_t batch,
+                     const rsp_measure_params* mp, rsp_measure_plan_t* out) {
+    if (!mp || !d_flag || !out || batch < 0) return fail(ctx, RSP_ERR_ARG, "rsp_measure_plan: bad argument");
+    int64_t ld = 0, cs = 0;
+    int rc = measure_check(ctx, "rsp_measure_plan", V, R, batch, mp, &ld, &cs);
+    if (rc) return rc;
+    const rsp::MeasPlan p = rsp::meas_plan(V, R, ld, cs, (uintptr_t)d_flag, rsp::measure_bands((int)V, (int)batch));
+    memset(out, 0, sizeof(*out));
+    out->wide = p.wide ? 1 : 0;
+    out->cw = p.cw;
+    out->groups = p.G;
+    out->slices = p.S;
+    out->rows = p.rows;
+    out->q = p.q;
+    out->passes = p.passes;
+    out->bands = p.bands;
+    return RSP_OK;
+}
+
 int rsp_motion_measure_dev(rsp_ctx* ctx, const float* d_sum, const float* d_diff, const uint8_t* d_flag, int64_t V,
                            int64_t R, int64_t batch, const rsp_measure_params* mp, const double* d_r_scale,
                            const double* d_v_scale, int64_t max_hits, double* d_est, int32_t* d_cells,
@@ -29,23 +74,9 @@ int rsp_motion_measure_dev(rsp_ctx* ctx, const float* d_sum, const float* d_diff
     if (!mp || !d_sum || !d_diff || !d_flag || !d_r_scale || !d_v_scale || !d_count || batch < 0 || max_hits < 0 ||
         (max_hits > 0 && !d_est))
         return fail(ctx, RSP_ERR_ARG, "rsp_motion_measure_dev: bad argument");
-    const int64_t n = 2 * (int64_t)mp->extra_dots + 1;
-    if (mp->extra_dots < 1 || mp->extra_dots > 4)
-        return fail(ctx, RSP_ERR_UNSUPPORTED, "rsp_motion_measure_dev: extra_dots %d outside 1..4", mp->extra_dots);
-    if (mp->r_interp < 1 || mp->r_interp > 64 || mp->v_interp < 1 || mp->v_interp > 64)
-        return fail(ctx, RSP_ERR_ARG, "rsp_motion_measure_dev: interpolation factors %d, %d outside 1..64",
-                    mp->r_interp, mp->v_interp);
-    if (V < 1 || R < 1 || V > (1 << 20) || R > (1 << 20) || V * R > (int64_t)1 << 31 || batch > 0x7fffffff)
-        return fail(ctx, RSP_ERR_ARG, "rsp_motion_measure_dev: bad shape %lld x %lld x %lld", (long long)batch,
-                    (long long)V, (long long)R);
-    if (R < n || mp->mtd0_num < 0 || V - 2 * (int64_t)mp->mtd0_num - 1 < n)
-        return fail(ctx, RSP_ERR_ARG,
-                    "rsp_motion_measure_dev: %lld range bins / %lld unzeroed rows are fewer than 2*extraDots+1",
-                    (long long)R, (long long)(V - 2 * (int64_t)mp->mtd0_num - 1));
-    const int64_t ld = mp->ld ? mp->ld : R, cs = mp->cpi_stride ? mp->cpi_stride : V * ld;
-    if (ld < R || cs < (V - 1) * ld + R)
-        return fail(ctx, RSP_ERR_ARG, "rsp_motion_measure_dev: row pitch %lld / CPI stride %lld too small for %lld x %lld",
-                    (long long)ld, (long long)cs, (long long)V, (long long)R);
+    int64_t ld = 0, cs = 0;
+    int vrc = measure_check(ctx, "rsp_motion_measure_dev", V, R, batch, mp, &ld, &cs);
+    if (vrc) return vrc;
     if (batch == 0) return RSP_OK;
     if (!set_device(ctx)) return fail(ctx, RSP_ERR_HIP, "hipSetDevice failed");
     rsp::MeasureArgs a;

@@ -35,7 +35,7 @@ EXPORTS = ("rsp_version", "rsp_create", "rsp_destroy", "rsp_last_error", "rsp_se
            "rsp_set_pc_prune", "rsp_set_lane_chunks", "rsp_pc_plan", "rsp_scr_dev", "rsp_inject_dev", "rsp_scr_gain",
            "rsp_cfar_plan", "rsp_legacy_record_bytes", "rsp_ingest_legacy_dev", "rsp_condense_dev", "rsp_cmap_dev",
            "rsp_cmap_plan", "rsp_spec_width_dev", "rsp_track_dev", "rsp_set_pc_rows", "rsp_get_pc_rows",
-           "rsp_os_cfar_dev", "rsp_os_cfar_plan")
+           "rsp_os_cfar_dev", "rsp_os_cfar_plan", "rsp_measure_plan")
 RSP_NKERNELS = 6
 KERNEL_NAMES = ("pc_kernel", "mtd_kernel", "cfar_r_kernel", "cfar_v_kernel", "os_v_kernel", "os_r_kernel")
 
@@ -93,6 +93,11 @@ class rsp_measure_params(C.Structure):
                 ("delta_v", C.c_double), ("k_value", C.c_double), ("beam_angle_step", C.c_double),
                 ("ele_comp", C.c_double), ("ele_sys_err", C.c_double), ("ld", C.c_int64),
                 ("cpi_stride", C.c_int64)]
+
+
+class rsp_measure_plan_t(C.Structure):
+    _fields_ = [("wide", C.c_int32), ("cw", C.c_int32), ("groups", C.c_int32), ("slices", C.c_int32),
+                ("rows", C.c_int32), ("q", C.c_int32), ("passes", C.c_int32), ("bands", C.c_int32)]
 
 
 class rsp_condense_params(C.Structure):
@@ -287,6 +292,8 @@ def load_library(path=None):
     lib.rsp_motion_measure_dev.restype = C.c_int
     lib.rsp_motion_measure_dev.argtypes = [vp, vp, vp, vp, i64, i64, i64, C.POINTER(rsp_measure_params), vp, vp,
                                            i64, vp, vp, vp, vp]
+    lib.rsp_measure_plan.restype = C.c_int
+    lib.rsp_measure_plan.argtypes = [vp, vp, i64, i64, i64, C.POINTER(rsp_measure_params), C.POINTER(rsp_measure_plan_t)]
     lib.rsp_condense_dev.restype = C.c_int
     lib.rsp_condense_dev.argtypes = [vp, vp, vp, i64, i64, i64, C.POINTER(rsp_condense_params), vp, i32, vp, vp, vp]
     lib.rsp_cmap_dev.restype = C.c_int

@@ -78,9 +78,10 @@ def test_measure_parity(meas, e, V, R):
 
 @pytest.mark.parametrize("V,R", [(64, 256), (96, 250)])
 def test_measure_large_batch_path(meas, V, R):
-    """batch >= 128: one workgroup per CPI (hits_kernel); smaller batches above run the banded
-    path (band_count / band_scan / band_list).  Same bit-exact bar on a sample of CPIs, and
-    every CPI's count equals its flag total."""
+    """A batch above the CU count.  Every batch size runs one workgroup per CPI (hits_kernel):
+    the banded path (band_count / band_scan / band_list) is compiled but out of the shipped
+    library's reach, measure_bands() returns 1 unless it is built with -DRSP_DEV_MEASURE_BANDS.
+    Same bit-exact bar on a sample of CPIs, and every CPI's count equals its flag total."""
     rng = np.random.default_rng(V + R)
     s, d, f = _scene(rng, 130, V, R, 0.002)
     kw = _kw(2, 5, R, V)
@@ -102,7 +103,8 @@ def test_measure_dense_and_truncated(meas):
 
 
 def test_measure_empty_and_large_columns(meas):
-    """No hits; then one CPI with R > 4096 (several column passes) and a V of 2048 (the DMX
+    """No hits; then one CPI with R > 4096 (512 column groups of 16: still a single column
+    pass, tests/test_gpu_measure_sweep.py holds the multi-pass cases) and a V of 2048 (the DMX
     Doppler size)."""
     V, R = 64, 512
     s = np.ones((1, V, R), np.float32)

@@ -8,10 +8,15 @@ what is pinned: MATLAB's interp1 'spline' = not-a-knot cubic spline (scipy Cubic
 independent implementation of that published definition), MATLAB's colon a:d:b, find()
 column-major order, and known-answer peaks (a sampled parabola, and a Gaussian whose true maximum is known).
 """
+import os
+import subprocess
+
 import numpy as np
 import pytest
 
 import measure_ref as mr
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.mark.parametrize("n", [5, 7, 9, 4, 6])
@@ -25,6 +30,13 @@ def test_spline_matches_scipy_not_a_knot(n):
     got = np.array([mr.spline_eval(y, m, ti) for ti in t])
     np.testing.assert_allclose(got, cs(t), rtol=0, atol=1e-12)
     np.testing.assert_allclose(m, cs(np.arange(n), 2), rtol=0, atol=1e-11)
+    # the samples of factors that are no power of two, at the oracle's own colon points (the
+    # abscissae refine() evaluates): the same absolute bar
+    for k in (3, 5, 7, 10, 63):
+        q = mr.colon(7.0, 1.0 / k, 7.0 + n - 1)
+        assert len(q) == (n - 1) * k + 1 and q[0] == 7.0 and q[-1] == 7.0 + n - 1
+        got = np.array([mr.spline_eval(y, m, qi - 7.0) for qi in q])
+        np.testing.assert_allclose(got, cs(q - 7.0), rtol=0, atol=1e-12)
 
 
 def test_spline_three_points_is_the_parabola():
@@ -145,3 +157,80 @@ def test_dmx_scales():
     assert dV == pytest.approx(lam * (1 / 52.08e-6) / 2048 / 2)
     assert vS.shape == (2048,) and vS[0] == 0 and vS[1] == pytest.approx(-dV) and vS[-1] == pytest.approx(dV)
     assert vS[1024] == pytest.approx(1024 * dV)          # fftshift puts -N/2 at index N/2
+
+
+# ---- the kernel's own arithmetic (csrc/rsp_measure_math.h) compiled for the host -----------------
+@pytest.fixture(scope="module")
+def math_check(tmp_path_factory):
+    """tests/native/measure_math_check.cpp: the header measure_kernel compiles, as a host program
+    (contraction off, as the header's pragma sets it for the device)."""
+    exe = str(tmp_path_factory.mktemp("mm") / "measure_math_check")
+    subprocess.run(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-Wall", "-Werror", "-I",
+                    os.path.join(ROOT, "radar-signal-process_amd", "csrc"),
+                    os.path.join(ROOT, "tests", "native", "measure_math_check.cpp"), "-o", exe], check=True,
+                   capture_output=True, text=True, timeout=300)
+
+    def run(mode, payload, tmp):
+        src, dst = str(tmp / (mode + ".in")), str(tmp / (mode + ".out"))
+        with open(src, "wb") as f:
+            f.write(payload)
+        r = subprocess.run([exe, mode, src, dst], capture_output=True, text=True, timeout=120)
+        assert r.returncode == 0, r.stderr[-2000:]
+        with open(dst, "rb") as f:
+            return f.read()
+    return run
+
+
+def _cell_sets(rng, n):
+    """The kinds of cell values a spline can meet: fp32-valued random, constant, quantised (many
+    equal neighbours), strictly monotone either way (the maximum at an end), all zero."""
+    f32 = lambda x: np.asarray(x, np.float32).astype(np.float64)      # noqa: E731
+    up = np.cumsum(rng.random(n) + 0.01)
+    return [f32(rng.random(n) * 2 + 0.1), np.full(n, float(np.float32(rng.random() + 0.5))),
+            f32(np.floor(rng.random(n) * 3) / 2), f32(up), f32(up[::-1]), np.zeros(n)]
+
+
+def test_refine_of_the_kernel_header_is_the_oracle_bit_for_bit(math_check, tmp_path):
+    """Every factor 1..64, e = 1..4 and first cell 1, 7, 2040 and 1048000 on each kind of cell set:
+    the header's refine() gives the bytes of measure_ref.refine.  For 53 of the 64 factors the
+    second half of MATLAB's colon is not a + i*d, so this is where an a + i*d slip, or a
+    contracted multiply-add, shows without a GPU."""
+    rng = np.random.default_rng(2024)
+    recs, want = [], []
+    for e in (1, 2, 3, 4):
+        n = 2 * e + 1
+        for first in (1, 7, 2040, 1048000):
+            cells = list(range(first, first + n))
+            for k in range(1, 65):
+                for y in _cell_sets(rng, n):
+                    recs.append(np.array([e, first, k, 0], np.int32).tobytes() + y.tobytes())
+                    want.append(mr.refine(y, cells, k))
+    got = np.frombuffer(math_check("refine", b"".join(recs), tmp_path), np.uint64)
+    want = np.array(want, np.float64)
+    assert got.shape == want.shape == (4 * 4 * 64 * 6,)
+    bad = np.nonzero(got != want.view(np.uint64))[0]
+    assert bad.size == 0, (bad.size, bad[:5].tolist(), got.view(np.float64)[bad[:5]].tolist(), want[bad[:5]].tolist())
+    assert (want != np.floor(want)).any()
+
+
+def test_fix_cells_of_the_kernel_header_is_the_oracle(math_check, tmp_path):
+    """fix_cells over every (center, e, lo, hi) of a small grid, size = 12: the same first cell, and
+    a refusal exactly where the oracle raises or its cells leave 1..size."""
+    size = 12
+    grid = [(c, e, lo, hi) for e in (1, 2, 3, 4) for c in range(1, size + 1) for lo in range(1, size + 1)
+            for hi in range(lo, size + 1)]
+    payload = np.array([(c, e, lo, hi, size) for c, e, lo, hi in grid], np.int32).tobytes()
+    got = np.frombuffer(math_check("fix", payload, tmp_path), np.int32).reshape(-1, 2)
+    assert len(got) == len(grid)
+    refused = 0
+    for (c, e, lo, hi), (ok, first) in zip(grid, got):
+        try:
+            cells = mr.fix_cells(c, e, lo, hi)
+            good = cells[0] >= 1 and cells[-1] <= size
+        except IndexError:
+            good = False
+        assert bool(ok) == good, (c, e, lo, hi)
+        if good:
+            assert first == cells[0], (c, e, lo, hi)
+        refused += not good
+    assert 0 < refused < len(grid)
