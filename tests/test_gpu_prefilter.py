@@ -1,7 +1,13 @@
 """GPU parity of the echo pre-filters (rsp_prefilter_dev) against the fp64
 restatement (oracle/prefilter_ref.py).  Bar: max |gpu - ref| / max |ref| <= 1e-6 (fp32
 products of fp32 inputs; the MTI difference is one fp32 subtraction, the gain one multiply),
-the zero rows exact; iSTC may run in place, MTI may not."""
+the zero rows exact; iSTC may run in place, MTI may not.
+
+The stand-alone kernels' own bar is exactness (test_lag_and_shape_sweep, test_grid_stride): one fp32
+subtraction and one fp32 multiply have one correct result each, so the output is bit-equal to numpy
+doing the same float32 operations in the same order, (x[m + lag] - x[m]) * g, across the lags (1, one
+that does not divide P, P - 1, P and beyond), R / 2 = 1, odd and past a wave, and launches larger
+than the 256 * 64 workgroups the launchers cap the grid at; the output lies between guard bytes."""
 import numpy as np
 import pytest
 
@@ -180,3 +186,118 @@ def test_fused_prefilter_off_is_identity():
         outs.append(r.cpu().numpy())
     assert np.array_equal(outs[0], outs[2]) and not np.array_equal(outs[0], outs[1])
     eng.close()
+
+
+# ------------------------------------------------------------------ exactness of the stand-alone kernels
+GUARD = 4096          # bytes of 0xA5 on each side of an output (a multiple of 16)
+
+
+def _gain(R):
+    """Positive, distinct in every column, a factor of about 1000 between neighbours: a column
+    off by one or a swapped pair changes every sample."""
+    c = np.arange(R, dtype=np.float64)
+    g = ((c + 1.0) * np.where(c % 2 == 0, 1.0, 1000.0)).astype(np.float32)
+    assert (g > 0).all() and len(np.unique(g)) == R
+    return g
+
+
+def _exact(x, lag, gain):
+    """The kernels' arithmetic in numpy float32, operation by operation: the difference, then the
+    product; rows from P - lag on are 0."""
+    v = np.ascontiguousarray(x).view(np.float32).reshape(x.shape + (2,))
+    P = x.shape[-2]
+    if lag > 0:
+        y = np.zeros_like(v)
+        if lag < P:
+            y[..., :P - lag, :, :] = v[..., lag:, :, :] - v[..., :P - lag, :, :]
+    else:
+        y = v.copy()
+    if gain is not None:
+        y = y * np.asarray(gain, np.float32)[:, None]
+    assert y.dtype == np.float32
+    return np.ascontiguousarray(y).view(np.complex64)[..., 0]
+
+
+def _bits(a):
+    return np.ascontiguousarray(a).view(np.uint32)
+
+
+def _guarded_out(torch, shape):
+    n = int(np.prod(shape)) * 8
+    raw = torch.full((2 * GUARD + n,), 0xA5, dtype=torch.uint8, device="cuda")
+    return raw, raw[GUARD:GUARD + n].view(torch.complex64).view(tuple(shape))
+
+
+def _apply_guarded(torch, pf, d_x, gain, lag, raw=None):
+    """apply_dev into the middle of a 0xA5-filled buffer -> the output; the guards must be intact."""
+    if raw is None:
+        raw, out = _guarded_out(torch, d_x.shape)
+    else:
+        raw.fill_(0xA5)
+        out = raw[GUARD:raw.numel() - GUARD].view(torch.complex64).view(tuple(d_x.shape))
+    pf.apply_dev(d_x, out=out, gain=gain, mti_lag=lag)
+    torch.cuda.synchronize()
+    assert bool((raw[:GUARD] == 0xA5).all()) and bool((raw[-GUARD:] == 0xA5).all()), "a guard byte was written"
+    return out.cpu().numpy()
+
+
+LAGS = [(7, 1), (7, 3), (7, 6), (7, 7), (7, 9), (61, 30), (64, 30)]
+
+
+@pytest.mark.parametrize("P,lag", LAGS)
+def test_lag_and_shape_sweep(pf, P, lag):
+    """mti_chain_kernel and prefilter_kernel at the edges of the lag (the smallest, one that does not
+    divide P, one live row, lag = P and lag > P: all zero, the default lag on an odd and on the
+    tested P) times R / 2 = 1, 3 and 35, gain off and on, three CPIs: bit-equal to _exact, the rows
+    from P - lag on exactly 0, the 1e-6 bar against the fp64 restatement as before, the input
+    unchanged, the guards intact; gain-only in place bit-equal to out of place."""
+    import torch
+    for R in (2, 6, 70):
+        x = _echo(np.random.default_rng(1000 * P + 10 * lag + R), 3, P, R)
+        d_x = torch.from_numpy(x).cuda()
+        g = _gain(R)
+        for gain in (None, g):
+            what = "P %d lag %d R %d gain %d" % (P, lag, R, gain is not None)
+            y = _apply_guarded(torch, pf, d_x, gain, lag)
+            want = _exact(x, lag, gain)
+            assert np.array_equal(_bits(y), _bits(want)), (what, int((_bits(y) != _bits(want)).sum()))
+            assert (_bits(y[:, max(P - lag, 0):]) == 0).all(), what
+            if lag < P:
+                assert y[:, :P - lag].all(), what       # every live sample is a difference of noise
+            scale = np.ones(R) if gain is None else gain.astype(np.float64)
+            for b in range(3):
+                assert _close(y[b], pr.fun_Process_MTI(x[b].astype(np.complex128), lag) * scale[None, :]), what
+            assert np.array_equal(_bits(d_x.cpu().numpy()), _bits(x)), what + ": the input was changed"
+        # gain only: out of place, then in place on a copy inside its own guards
+        y = _apply_guarded(torch, pf, d_x, g, 0)
+        assert np.array_equal(_bits(y), _bits(_exact(x, 0, g)))
+        raw, d = _guarded_out(torch, x.shape)
+        d.copy_(d_x)
+        pf.apply_dev(d, out=d, gain=g)
+        torch.cuda.synchronize()
+        assert bool((raw[:GUARD] == 0xA5).all()) and bool((raw[-GUARD:] == 0xA5).all())
+        assert np.array_equal(_bits(d.cpu().numpy()), _bits(y))
+        assert np.array_equal(_bits(d_x.cpu().numpy()), _bits(x))
+
+
+def test_grid_stride(pf):
+    """Launches past the launchers' cap of 256 * 64 workgroups of 256 threads (4 194 304 items), so
+    that the grid-stride loops go round: one [3, 33, 88000] echo, gain only (4 356 000 sample pairs),
+    MTI with lag 32 (3 * 32 * 44000 = 4 224 000 chain items), and both.  Bit-equal to _exact; with
+    lag 32 of 33 pulses row 0 alone is live and the last row exactly 0."""
+    import torch
+    B, P, R, lag = 3, 33, 88000, 32
+    cap = 256 * 64 * 256
+    assert B * P * (R // 2) > cap and B * min(lag, P) * (R // 2) > cap
+    x = _echo(np.random.default_rng(88000), B, P, R)
+    d_x = torch.from_numpy(x).cuda()
+    g = _gain(R)
+    raw, _ = _guarded_out(torch, x.shape)
+    for gain, lg in ((g, 0), (None, lag), (g, lag)):
+        y = _apply_guarded(torch, pf, d_x, gain, lg, raw)
+        want = _exact(x, lg, gain)
+        diff = _bits(y) != _bits(want)
+        assert not diff.any(), (gain is not None, lg, int(diff.sum()), np.argwhere(diff)[0])
+        if lg:
+            assert (_bits(y[:, P - 1]) == 0).all() and (_bits(y[:, P - lg:]) == 0).all() and y[:, 0].all()
+    assert np.array_equal(_bits(d_x.cpu().numpy()), _bits(x))
