@@ -57,7 +57,8 @@ extern "C" {
                                   takes the arrays' length, rsp_profile_read writes exactly the 4
                                   ABI-3 entries;
                                5: rsp_score_dev / rsp_score_summary with rsp_score_params and
-                                  rsp_score_result added */
+                                  rsp_score_result added; rsp_integrate_dev / rsp_binint_dev with
+                                  rsp_integ_params are an addition within 5 */
 #define RSP_MAX_SEG 4
 #define RSP_MAX_FIR_TAPS 64
 
@@ -923,6 +924,80 @@ int rsp_track_dev(rsp_ctx* ctx, const double* d_est /* [batch][max_hits][3] */,
                   int32_t* d_meta /* [slots][2] */, int32_t* d_assign /* [batch][max_hits] */,
                   double* d_snap_f /* [batch][max_tracks][4] or NULL */, int32_t* d_snap_i /* same, [8] */,
                   int32_t* d_tcount /* [batch][8] */, void* stream);
+
+/* ---- post-detection integration over the CPIs of a dwell ----------------------------------- */
+/* Every detector here decides on one CPI alone; only rsp_track_dev looks across CPIs, after hard
+ * decisions.  A target below the threshold in every CPI of a dwell is lost.  These two calls are the
+ * classical answer, between the MTD and the CFAR (the reference ships no such stage):
+ *   rsp_integrate_dev  video (non-coherent) integration: the amplitude planes of the last n CPIs are
+ *                      summed before the CFAR;
+ *   rsp_binint_dev     binary (M-of-N) integration: the flag planes of the last n CPIs are counted
+ *                      after the CFAR.
+ * The RDM orders the cells by velocity, so Doppler row v has a known range walk per CPI (a DMX frame
+ * is 80 ms and a range cell 12 m: 150 m/s is one cell per CPI); each past plane is shifted row by row
+ * before it is added, and the target piles up in one cell instead of smearing over n.
+ *
+ * d_in, d_out: [batch][V][ld] windows of R columns (float32 / uint8), geometry as rsp_os_params'.
+ * Like the clutter map and the tracker the stage carries state from call to call in the caller's
+ * memory: d_hist [slots][n-1][V][R], a ring of the last n-1 input planes of each slot, stored dense
+ * (window columns only), and d_meta int32 [slots][2] = {cpis, 0}.
+ *
+ * CPI b of a batch, in batch order.  s = d_slot[b] (0 when d_slot is NULL).
+ *   s < 0 or s >= slots: the CPI touches no state, n_eff = 1: it is integrated as the first CPI of a
+ *     slot would be.
+ *   otherwise k = d_meta[2s], the CPIs the slot has seen (a negative count reads as 0), and
+ *     n_eff = min(n, k + 1).  x_0 is the CPI itself, x_i (1 <= i < n_eff) the plane i CPIs back on
+ *     the slot.
+ *   A target that stood at column c of row v i CPIs ago stands at c + d_shift[(i-1)*V + v] now (0 when
+ *   d_shift is NULL): the term of x_i at (v, r) is x_i[v][r - shift].  A source column outside [0, R)
+ *   gives +0.0f (no hit in the binary form): nothing wraps, nothing crosses the window's column edges,
+ *   any int32 shift is legal.
+ *   sum     acc = x_0[v][r]; acc = acc + term_i for i = 1 .. n_eff-1 in that order, every addition a
+ *           separate fp32 add; an out-of-window term is added as +0.0f, not skipped; NaN and Inf
+ *           propagate as IEEE says.  d_out[v][r] = acc.  The result is a sum, not a mean: the first
+ *           n-1 CPIs of a slot come out at a smaller scale than the later ones.  Every consumer here
+ *           (the CFARs, the measurement, the width) compares ratios inside one plane, so that scale
+ *           does not matter to them; a caller that wants a mean divides by d_neff.
+ *   binary  cnt = (x_0[v][r] != 0) plus one for each i >= 1 for which any of the columns
+ *           r - shift - spread .. r - shift + spread that lie inside the window is nonzero in x_i[v];
+ *           d_out[v][r] = cnt >= m ? 1 : 0.  Strict: with m > 1 a slot flags nothing before its m-th CPI.
+ *   state   d_neff[b] = n_eff.  In-range slot: with n > 1 the input plane becomes ring entry
+ *           k mod (n-1) of the slot; then d_meta[2s] = k + 1 (also with n = 1, which keeps no planes).
+ *           Ring entries that are not overwritten keep their bytes, d_meta[2s+1] is not touched.
+ *           Reset = zeroing d_meta; d_hist need not be cleared, n_eff never reaches an entry that was
+ *           not written since the reset.
+ * d_out, d_neff, d_hist and d_meta after a sequence of CPIs are the same bytes in one batch as in any
+ * split into consecutive calls, and the same from run to run (no atomics, nothing combined across
+ * threads).  Only window columns of d_out are written.
+ *
+ * Refused with RSP_ERR_ARG and a message, before the context is looked at: a NULL params, d_in,
+ * d_meta or d_out, d_hist NULL with n > 1; n outside 1..16; sum form with m or spread nonzero,
+ * binary form with m outside 1..n or spread outside 0..2; reserved != 0; ld < R or a CPI stride
+ * below a plane; slots outside 1..65535; misaligned pointers; d_out overlapping d_in or d_hist (in
+ * place is not allowed: later CPIs of a batch read earlier input planes), d_in overlapping d_hist.
+ * Asynchronous on `stream`; works on any context, the CFAR-only kind included.  Three launches
+ * (plan, integrate, ring update); nothing is allocated, freed or copied synchronously
+ * in the launch path except growth of the context's plan table (batch * (n + 3) ints, grow-only). */
+#define RSP_INTEG_MAX_N 16
+typedef struct {
+    int32_t n;          /* 1..16: the CPI itself and the n-1 before it on its slot */
+    int32_t m;          /* binary form: 1..n; sum form: 0 */
+    int32_t spread;     /* binary form: 0..2 columns; sum form: 0 */
+    int32_t reserved;   /* 0 */
+    int64_t ld;         /* row pitch of d_in and d_out in elements (0 = R) */
+    int64_t cpi_stride; /* elements between CPIs of d_in and d_out (0 = V * ld) */
+} rsp_integ_params;
+
+int rsp_integrate_dev(rsp_ctx* ctx, const float* d_in, int64_t V, int64_t R, int64_t batch,
+                      const rsp_integ_params* ip, const int32_t* d_shift /* [n-1][V] or NULL */,
+                      const int32_t* d_slot /* [batch] or NULL */, int32_t slots,
+                      float* d_hist /* [slots][n-1][V][R]; NULL only when n == 1 */,
+                      int32_t* d_meta /* [slots][2] = {cpis, 0} */,
+                      float* d_out, int32_t* d_neff /* [batch] or NULL */, void* stream);
+
+int rsp_binint_dev(rsp_ctx* ctx, const uint8_t* d_in, int64_t V, int64_t R, int64_t batch,
+                   const rsp_integ_params* ip, const int32_t* d_shift, const int32_t* d_slot, int32_t slots,
+                   uint8_t* d_hist, int32_t* d_meta, uint8_t* d_out, int32_t* d_neff, void* stream);
 
 /* ---- detection scoring against truth (main_cfar.m's evaluation functions) ---------------- */
 /* The four local functions at the end of MatlabProcess_xuzerui/CFAR_WangCai/main_cfar.m, the

@@ -73,6 +73,7 @@ struct rsp_ctx {
     DevBuf scr_ps;                      // injection: per-CPI sums, ratios and pulse phases (InjectArgs::ps)
     DevBuf cond_tmp;                    // condensation: labels, keys and hit lists of one chunk of CPIs
     DevBuf cmap_band;                   // clutter map: the band amplitudes of a call without d_band
+    DevBuf integ_plan;                  // integration: where each CPI's past planes live (grow-only)
     // clutter map: window x DFT tables [P][kpad] by {P, V, window, beta bits, q_lo, q_hi, kpad} (in `owned`)
     std::map<std::vector<int64_t>, float2*> cmap_tab;
     DevBuf ing_meta;                    // ingest: per-PRT record offsets and types

@@ -278,6 +278,21 @@ hipError_t launch_track(const double* est, const int32_t* count, int64_t batch, 
                         const double* dt, double* state_f, int32_t* state_i, int32_t* meta, int32_t* assign,
                         double* snap_f, int32_t* snap_i, int32_t* tcount, hipStream_t st);
 
+// Post-detection integration (rsp_integ.hip): rsp_integ_params with the shape and the resolved pitches.
+struct IntegArgs {
+    int V, R;
+    int n, m, spread;      // m, spread: the binary form's (0 for the sum)
+    int slots;
+    int64_t ld, cs;        // row pitch and CPI stride of the input and output planes, in elements
+};
+// The plan table of a call: batch rows of n + 3 ints.
+size_t integ_plan_bytes(int64_t batch, int n);
+// Plan, integrate, ring update.  shift, slot, neff may be null; hist only when n == 1.
+hipError_t launch_integ_sum(const float* in, float* hist, const int32_t* shift, const int32_t* slot, int32_t* meta,
+                            int32_t* plan, float* out, int32_t* neff, int64_t batch, const IntegArgs& a, hipStream_t st);
+hipError_t launch_integ_bin(const uint8_t* in, uint8_t* hist, const int32_t* shift, const int32_t* slot, int32_t* meta,
+                            int32_t* plan, uint8_t* out, int32_t* neff, int64_t batch, const IntegArgs& a, hipStream_t st);
+
 // Detection scoring (rsp_score.hip): rsp_score_params with the shape and the resolved pitches.
 struct ScoreArgs {
     int V, R;

@@ -1,8 +1,8 @@
 // rsp_stages.cpp -- the C ABI's stage entry points around the chain (include/rsp.h): post-detection
 // measurement, plot condensation, clutter map, Doppler line width, detection scoring, echo pre-filters, target
-// injection, raw-data ingest, the legacy record ingest and tracking.  Each validates its arguments and
-// launches its stage's kernels (rsp_<stage>.hip); the context, the presets and the PC -> MTD ->
-// CFAR chain are in rsp_capi.cpp.
+// injection, raw-data ingest, the legacy record ingest, tracking and post-detection integration.  Each
+// validates its arguments and launches its stage's kernels (rsp_<stage>.hip); the context, the presets
+// and the PC -> MTD -> CFAR chain are in rsp_capi.cpp.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -800,4 +800,96 @@ int rsp_track_dev(rsp_ctx* ctx, const double* d_est, const int32_t* d_count, int
     HIP_TRY(ctx, rsp::launch_track(d_est, d_count, batch, a, d_slot, d_dt, d_state_f, d_state_i, d_meta, d_assign,
                                    d_snap_f, d_snap_i, d_tcount, (hipStream_t)stream));
     return RSP_OK;
+}
+
+// ------------------------------------------------------------------ post-detection integration
+// Both forms: everything is checked on the host before the context is looked at; `esz` is the element size
+// (4: the sum form, 1: the binary form).
+static int integ_check(rsp_ctx* ctx, const char* who, int esz, const void* d_in, int64_t V, int64_t R, int64_t batch,
+                       const rsp_integ_params* ip, const int32_t* d_shift, const int32_t* d_slot, int32_t slots,
+                       const void* d_hist, const int32_t* d_meta, const void* d_out, const int32_t* d_neff,
+                       rsp::IntegArgs* a) {
+    if (!ip || !d_in || !d_meta || !d_out)
+        return fail(ctx, RSP_ERR_ARG, "%s: null %s", who, !ip ? "params" : !d_in ? "d_in" : !d_meta ? "d_meta" : "d_out");
+    if (V < 1 || R < 1 || V > (1 << 20) || R > (1 << 20) || V * R > (int64_t)1 << 31 || batch < 0 || batch > 0x7fffffff)
+        return fail(ctx, RSP_ERR_ARG, "%s: bad shape %lld x %lld x %lld", who, (long long)batch, (long long)V, (long long)R);
+    if (ip->n < 1 || ip->n > RSP_INTEG_MAX_N)
+        return fail(ctx, RSP_ERR_ARG, "%s: n = %d outside 1..%d", who, ip->n, RSP_INTEG_MAX_N);
+    if (esz == 4 && (ip->m != 0 || ip->spread != 0))
+        return fail(ctx, RSP_ERR_ARG, "%s: m = %d, spread = %d (both 0 in the sum form)", who, ip->m, ip->spread);
+    if (esz == 1 && (ip->m < 1 || ip->m > ip->n))
+        return fail(ctx, RSP_ERR_ARG, "%s: m = %d outside 1..n = %d", who, ip->m, ip->n);
+    if (esz == 1 && (ip->spread < 0 || ip->spread > 2))
+        return fail(ctx, RSP_ERR_ARG, "%s: spread = %d outside 0..2", who, ip->spread);
+    if (ip->reserved != 0) return fail(ctx, RSP_ERR_ARG, "%s: reserved = %d", who, ip->reserved);
+    const int64_t ld = ip->ld ? ip->ld : R, cs = ip->cpi_stride ? ip->cpi_stride : V * ld;
+    if (ld < R || cs < (V - 1) * ld + R || (batch > 0 && cs > ((int64_t)1 << 60) / batch))
+        return fail(ctx, RSP_ERR_ARG, "%s: row pitch %lld / CPI stride %lld too small for %lld x %lld", who, (long long)ld,
+                    (long long)cs, (long long)V, (long long)R);
+    if (slots < 1 || slots > 65535) return fail(ctx, RSP_ERR_ARG, "%s: slots = %d outside 1..65535", who, slots);
+    if (ip->n > 1 && !d_hist) return fail(ctx, RSP_ERR_ARG, "%s: null d_hist with n = %d", who, ip->n);
+    if (esz == 4 && (((uintptr_t)d_in | (uintptr_t)d_hist | (uintptr_t)d_out) & 3))
+        return fail(ctx, RSP_ERR_ARG, "%s: misaligned plane (floats: 4 bytes)", who);
+    if (((uintptr_t)d_shift | (uintptr_t)d_slot | (uintptr_t)d_meta | (uintptr_t)d_neff) & 3)
+        return fail(ctx, RSP_ERR_ARG, "%s: misaligned argument (ints: 4 bytes)", who);
+    // in place is not allowed: later CPIs of a batch read earlier input planes
+    const int64_t span = batch > 0 ? ((batch - 1) * cs + (V - 1) * ld + R) * esz : 0;
+    const int64_t hspan = d_hist ? (int64_t)slots * (ip->n - 1) * V * R * esz : 0;
+    if (span > 0 && ranges_overlap(d_out, span, d_in, span)) return fail(ctx, RSP_ERR_ARG, "%s: d_out overlaps d_in", who);
+    if (span > 0 && hspan > 0 && ranges_overlap(d_out, span, d_hist, hspan))
+        return fail(ctx, RSP_ERR_ARG, "%s: d_out overlaps d_hist", who);
+    if (span > 0 && hspan > 0 && ranges_overlap(d_in, span, d_hist, hspan))
+        return fail(ctx, RSP_ERR_ARG, "%s: d_in overlaps d_hist", who);
+    a->V = (int)V;
+    a->R = (int)R;
+    a->n = ip->n;
+    a->m = ip->m;
+    a->spread = ip->spread;
+    a->slots = slots;
+    a->ld = ld;
+    a->cs = cs;
+    return RSP_OK;
+}
+
+// The plan table from the context's pool (grow-only), ordered after the previous call's use of it.
+static int integ_pool(rsp_ctx* ctx, int64_t batch, int n, hipStream_t st, int32_t** plan) {
+    int rc = scratch_acquire(ctx, st);
+    if (rc) return rc;
+    if ((rc = ensure(ctx, ctx->integ_plan, rsp::integ_plan_bytes(batch, n))) != RSP_OK) return rc;
+    *plan = (int32_t*)ctx->integ_plan.p;
+    return RSP_OK;
+}
+
+int rsp_integrate_dev(rsp_ctx* ctx, const float* d_in, int64_t V, int64_t R, int64_t batch, const rsp_integ_params* ip,
+                      const int32_t* d_shift, const int32_t* d_slot, int32_t slots, float* d_hist, int32_t* d_meta,
+                      float* d_out, int32_t* d_neff, void* stream) {
+    const char* who = "rsp_integrate_dev";
+    rsp::IntegArgs a{};
+    int rc = integ_check(ctx, who, 4, d_in, V, R, batch, ip, d_shift, d_slot, slots, d_hist, d_meta, d_out, d_neff, &a);
+    if (rc) return rc;
+    if (!ctx) return fail(nullptr, RSP_ERR_ARG, "%s: null ctx", who);
+    if (batch == 0) return RSP_OK;
+    if (!set_device(ctx)) return fail(ctx, RSP_ERR_HIP, "hipSetDevice failed");
+    hipStream_t st = (hipStream_t)stream;
+    int32_t* plan = nullptr;
+    if ((rc = integ_pool(ctx, batch, a.n, st, &plan))) return rc;
+    HIP_TRY(ctx, rsp::launch_integ_sum(d_in, d_hist, d_shift, d_slot, d_meta, plan, d_out, d_neff, batch, a, st));
+    return scratch_release(ctx, st);
+}
+
+int rsp_binint_dev(rsp_ctx* ctx, const uint8_t* d_in, int64_t V, int64_t R, int64_t batch, const rsp_integ_params* ip,
+                   const int32_t* d_shift, const int32_t* d_slot, int32_t slots, uint8_t* d_hist, int32_t* d_meta,
+                   uint8_t* d_out, int32_t* d_neff, void* stream) {
+    const char* who = "rsp_binint_dev";
+    rsp::IntegArgs a{};
+    int rc = integ_check(ctx, who, 1, d_in, V, R, batch, ip, d_shift, d_slot, slots, d_hist, d_meta, d_out, d_neff, &a);
+    if (rc) return rc;
+    if (!ctx) return fail(nullptr, RSP_ERR_ARG, "%s: null ctx", who);
+    if (batch == 0) return RSP_OK;
+    if (!set_device(ctx)) return fail(ctx, RSP_ERR_HIP, "hipSetDevice failed");
+    hipStream_t st = (hipStream_t)stream;
+    int32_t* plan = nullptr;
+    if ((rc = integ_pool(ctx, batch, a.n, st, &plan))) return rc;
+    HIP_TRY(ctx, rsp::launch_integ_bin(d_in, d_hist, d_shift, d_slot, d_meta, plan, d_out, d_neff, batch, a, st));
+    return scratch_release(ctx, st);
 }

@@ -9,11 +9,13 @@ front of it, the injection of simulated targets at a set SCR (rsp.inject).  Besi
 rsp.cmap detects in the zero-velocity band the chain blanks, against a clutter map, and
 rsp.width measures how wide the Doppler line of a detection's range column stands.  Behind the
 measurement, rsp.track joins the estimates of successive CPIs into tracks.  rsp.oscfar is a second
-detector beside the chain's cell-averaging CFAR: the ordered-statistic one.
+detector beside the chain's cell-averaging CFAR: the ordered-statistic one.  rsp.integrate sums or
+counts the planes of the last CPIs of a dwell, range walk compensated, around either detector.
 """
-from . import _capi, cmap, oscfar, presets, synth, track, width  # noqa: F401
+from . import _capi, cmap, integrate, oscfar, presets, synth, track, width  # noqa: F401
 from ._capi import RspError, load_library  # noqa: F401
 from .cmap import ClutterMap, band_of  # noqa: F401
+from .integrate import Integrator, walk_shifts  # noqa: F401
 from .oscfar import OsCfar  # noqa: F401
 from .track import Tracker  # noqa: F401
 from .width import Width, ampConstrWidthEst, width_dots  # noqa: F401

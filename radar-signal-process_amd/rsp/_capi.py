@@ -35,7 +35,7 @@ EXPORTS = ("rsp_version", "rsp_create", "rsp_destroy", "rsp_last_error", "rsp_se
            "rsp_set_pc_prune", "rsp_set_lane_chunks", "rsp_pc_plan", "rsp_scr_dev", "rsp_inject_dev", "rsp_scr_gain",
            "rsp_cfar_plan", "rsp_legacy_record_bytes", "rsp_ingest_legacy_dev", "rsp_condense_dev", "rsp_cmap_dev",
            "rsp_cmap_plan", "rsp_spec_width_dev", "rsp_track_dev", "rsp_set_pc_rows", "rsp_get_pc_rows",
-           "rsp_os_cfar_dev", "rsp_os_cfar_plan", "rsp_measure_plan")
+           "rsp_os_cfar_dev", "rsp_os_cfar_plan", "rsp_measure_plan", "rsp_integrate_dev", "rsp_binint_dev")
 RSP_NKERNELS = 6
 KERNEL_NAMES = ("pc_kernel", "mtd_kernel", "cfar_r_kernel", "cfar_v_kernel", "os_v_kernel", "os_r_kernel")
 
@@ -152,6 +152,14 @@ class rsp_track_params(C.Structure):
                 ("drop_tentative", C.c_int32), ("drop_confirmed", C.c_int32), ("reserved", C.c_int32),
                 ("dt", C.c_double), ("rate_sign", C.c_double), ("gate_r", C.c_double), ("gate_v", C.c_double),
                 ("alpha_r", C.c_double), ("alpha_v", C.c_double), ("alpha_e", C.c_double)]
+
+
+RSP_INTEG_MAX_N = 16
+
+
+class rsp_integ_params(C.Structure):
+    _fields_ = [("n", C.c_int32), ("m", C.c_int32), ("spread", C.c_int32), ("reserved", C.c_int32),
+                ("ld", C.c_int64), ("cpi_stride", C.c_int64)]
 
 
 class rsp_score_params(C.Structure):
@@ -311,6 +319,9 @@ def load_library(path=None):
     lib.rsp_track_dev.restype = C.c_int
     lib.rsp_track_dev.argtypes = [vp, vp, vp, i64, i64, C.POINTER(rsp_track_params), vp, vp, i32, vp, vp, vp, vp, vp,
                                   vp, vp, vp]
+    for fn in (lib.rsp_integrate_dev, lib.rsp_binint_dev):
+        fn.restype = C.c_int
+        fn.argtypes = [vp, vp, i64, i64, i64, C.POINTER(rsp_integ_params), vp, vp, i32, vp, vp, vp, vp, vp]
     lib.rsp_score_dev.restype = C.c_int
     lib.rsp_score_dev.argtypes = [vp, vp, vp, i64, i64, i64, C.POINTER(rsp_score_params), vp, vp, vp]
     lib.rsp_score_summary.restype = C.c_int

@@ -70,6 +70,8 @@ class DmxFrameProcessor:
         self._tracker = None
         self._track_opts = None
         self._os = None
+        self._integ = {}
+        self._integ_opts = None
 
     def close(self):
         self.eng.close()
@@ -121,6 +123,66 @@ class DmxFrameProcessor:
             out[(part, fk, "tracks")] = self._tracker.update_dev(est, count, slot=slot)
         return out
 
+    def reset_integration(self):
+        """Forget the CPIs of process_dev(integrate=...): the next call starts every ring anew."""
+        for integ in self._integ.values():
+            integ.reset()
+
+    def _integrate_options(self, integrate):
+        """integrate=dict(...) as (n, shift, m, spread): shift the int32 [n-1][V] walk table, or None."""
+        from .integrate import walk_shifts
+        integrate = dict(integrate)
+        n = int(integrate.pop("n", 4))
+        walk = bool(integrate.pop("walk", True))
+        rate_sign = float(integrate.pop("rate_sign", 1.0))
+        dt = float(integrate.pop("dt", self.spec.P / self.spec.radar["prf"]))
+        m = integrate.pop("m", None)
+        spread = int(integrate.pop("spread", 0))
+        if integrate:
+            raise TypeError("process_dev: integrate takes n, walk, rate_sign, dt, m and spread, not %s" % sorted(integrate))
+        shift = walk_shifts(self.scales[2], dt, self.scales[3], n, rate_sign) if walk and n > 1 else None
+        return n, shift, (None if m is None else int(m)), spread
+
+    def _integrator(self, part, plane, n, m=None, spread=0):
+        """The processor's Integrator of one (part, plane), on the engine's context."""
+        from .integrate import Integrator
+        if (part, plane) not in self._integ:
+            self._integ[(part, plane)] = Integrator(engine=self.eng, n=n, m=m, spread=spread)
+        return self._integ[(part, plane)]
+
+    def _integrate(self, echo, out, opts, detector, with_flagV):
+        """PC and MTD only, the sum and diff planes integrated per part, the flags from the integrated
+        sum (and, with m, counted over the CPIs)."""
+        import torch
+        n, shift, m, spread = opts
+        key = (n, m, spread)
+        if key != self._integ_opts:
+            self._integ = {}
+            self._integ_opts = key
+        ps, R_out = self.spec.cfar_segments[0][1], self.spec.R_out
+        parts = (("short", (0, ps)), ("long", (ps, R_out)))
+        out["sum_cpi"], out["diff_cpi"] = torch.empty_like(out["sum"]), torch.empty_like(out["diff"])
+        self.eng.run_dev(echo, rdm=out["sum_cpi"], diff=out["diff_cpi"], cfar=None)
+        # the parts are separate column windows: both start near zero range, no walk may cross column ps
+        for plane in ("sum", "diff"):
+            for part, cols in parts:
+                self._integrator(part, plane, n).sum_dev(out[plane + "_cpi"], shift=shift, cols=cols, out=out[plane])
+        if detector is None:
+            self.eng.cfar_dev(out["sum"], out["flag"], flagV=out["flagV"] if with_flagV else None, cfar=self.cfar)
+        else:
+            from .oscfar import OsCfar
+            if self._os is None:
+                self._os = OsCfar(engine=self.eng)
+            self._os.detect_dev(out["sum"], detector[0], detector[1], detector[2], flag=out["flag"], flagV=out["flagV"])
+        if m is not None:
+            for fk in ("flag", "flagV") if with_flagV or detector is not None else ("flag",):
+                out[fk + "_cpi"] = out[fk]
+                out[fk] = torch.empty_like(out[fk])
+                for part, cols in parts:
+                    self._integrator(part, fk, n, m, spread).count_dev(out[fk + "_cpi"], shift=shift, cols=cols,
+                                                                         out=out[fk])
+        return out
+
     def _detector_options(self, detector):
         """detector=dict(...) as (cfar, k, union): the preset's CFAR with T replaced when given."""
         import dataclasses
@@ -136,7 +198,7 @@ class DmxFrameProcessor:
         return cfar, k, union
 
     def process_dev(self, echo, beamPosNum, with_flagV=True, max_hits=4096, condense=None, width=None, track=None,
-                    detector=None):
+                    detector=None, integrate=None):
         """echo: complex64 [batch][2][P][R] (left, right) on the device.  Returns a dict of
         device outputs: the planes (sum, diff, flag, flagV) and, per part ('short', 'long') and
         flag kind ('flag', 'flagV'), (est, cells, count) as Measure.measure_dev gives them.
@@ -170,8 +232,24 @@ class DmxFrameProcessor:
         compression and the MTD only, and flag / flagV come from one ordered-statistic CFAR call
         (OsCfar.detect_dev) over the whole sum plane with the preset's window, M0 and segments (T
         defaults to the preset's).  The measurement, condense, width and track run on those flags
-        unchanged; flagV is always computed.  detector=None leaves the chain's own CFAR."""
+        unchanged; flagV is always computed.  detector=None leaves the chain's own CFAR.
+
+        integrate = dict(n=4, walk=True, rate_sign=1.0, dt=P/prf, m=None, spread=0): post-detection
+        integration over the last n CPIs (rsp.integrate).  The chain runs pulse
+        compression and the MTD only; out['sum_cpi'] / out['diff_cpi'] keep the per-CPI planes and
+        out['sum'] / out['diff'] are their sums over the last n CPIs, the short and the long part as
+        separate column windows, each past plane shifted row by row by its Doppler row's range walk
+        (walk_shifts of vScale, dt and deltaR; walk=False: no shift).  The flags come from
+        Engine.cfar_dev on the integrated sum with the preset's CFAR, or from `detector` when that is
+        given as well; with m set they then pass the binary integration (at least m of the last n
+        CPIs, within `spread` columns of the walked-back cell), out['flag_cpi'] / out['flagV_cpi']
+        keeping what went in.  Condense, measure, width and track run unchanged on the results.  The
+        processor holds one Integrator per (part, plane): the batches of successive calls are
+        consecutive in time, reset_integration() clears the rings, and a call whose n, m or spread
+        differ from the previous call's starts anew.  integrate=None leaves every output as it is."""
         import torch
+        if integrate is not None:
+            integrate = self._integrate_options(integrate)
         if detector is not None:
             detector = self._detector_options(detector)
         if track is not None:
@@ -187,7 +265,9 @@ class DmxFrameProcessor:
         dev = self.device
         out = {k: torch.empty(shp, dtype=t, device=dev) for k, t in
                (("sum", torch.float32), ("diff", torch.float32), ("flag", torch.uint8), ("flagV", torch.uint8))}
-        if detector is None:
+        if integrate is not None:
+            self._integrate(echo, out, integrate, detector, with_flagV)
+        elif detector is None:
             self.eng.run_dev(echo, rdm=out["sum"], diff=out["diff"], flag=out["flag"],
                              flagV=out["flagV"] if with_flagV else None, cfar=self.cfar)
         else:
@@ -252,7 +332,7 @@ class DmxFrameProcessor:
         return out
 
     def process_records_dev(self, d_stream, nbytes, nframes, with_flagV=True, max_hits=4096, condense=None,
-                            width=None, track=None, detector=None):
+                            width=None, track=None, detector=None, integrate=None):
         """:307-310 + process_dev from the record bytes: d_stream holds nframes * P consecutive
         legacy records (uint8 on the device, 4-byte aligned; the layout assumed for this waveform,
         see the module docstring), decoded into [nframes][2][P][R] without leaving HBM.  As the main
@@ -263,8 +343,8 @@ class DmxFrameProcessor:
         process_dev measures a batch at one beam position, so the frames are processed in runs of
         consecutive frames that share beamPosNum.  Returns a list with one dict per run:
         process_dev's outputs for the run's frames plus 'frames' (first, end), 'beamPosNum',
-        'frameInd' (int64 [n]) and 'angleCode' (float64 [n][P], host).  condense, width, track, detector:
-        as process_dev's; the runs at different beamPosNum feed the same track slots, because the frames
+        'frameInd' (int64 [n]) and 'angleCode' (float64 [n][P], host).  condense, width, track, detector,
+        integrate: as process_dev's; the runs at different beamPosNum feed the same track slots, because the frames
         are consecutive in time and eleAngleEst is absolute."""
         from . import _capi as capi
         from .ingest import LegacyIngest
@@ -287,7 +367,8 @@ class DmxFrameProcessor:
         for b in range(1, F + 1):
             if b == F or bpn[b] != bpn[a]:
                 out = self.process_dev(echo[a:b], int(bpn[a]), with_flagV=with_flagV, max_hits=max_hits,
-                                       condense=condense, width=width, track=track, detector=detector)
+                                       condense=condense, width=width, track=track, detector=detector,
+                                       integrate=integrate)
                 out.update(frames=(a, b), beamPosNum=int(bpn[a]), frameInd=frame_ind[a:b], angleCode=code[a:b])
                 runs.append(out)
                 a = b
