@@ -58,7 +58,8 @@ extern "C" {
                                   ABI-3 entries;
                                5: rsp_score_dev / rsp_score_summary with rsp_score_params and
                                   rsp_score_result added; rsp_integrate_dev / rsp_binint_dev with
-                                  rsp_integ_params are an addition within 5 */
+                                  rsp_integ_params are an addition within 5, as are
+                                  rsp_beam_fuse_dev / rsp_beam_elev_dev with rsp_fuse_params */
 #define RSP_MAX_SEG 4
 #define RSP_MAX_FIR_TAPS 64
 
@@ -998,6 +999,94 @@ int rsp_integrate_dev(rsp_ctx* ctx, const float* d_in, int64_t V, int64_t R, int
 int rsp_binint_dev(rsp_ctx* ctx, const uint8_t* d_in, int64_t V, int64_t R, int64_t batch,
                    const rsp_integ_params* ip, const int32_t* d_shift, const int32_t* d_slot, int32_t slots,
                    uint8_t* d_hist, int32_t* d_meta, uint8_t* d_out, int32_t* d_neff, void* stream);
+
+/* ---- stacked beams: the hits fused per cell, elevation from the beam amplitudes ------------- */
+/* The v2 capture forms a stack of elevation beams, and rsp_window_pc_mtd_cfar_dev gives one RDM and
+ * one flag plane per beam.  A target is flagged in two or three neighbouring beams at the same
+ * (v, r), or in all of them through sidelobes; the reference stops there
+ * (main_produce_dataset_win_xzr_v2.m:146-162 saves the planes).  These two calls merge the flags per
+ * cell, say which beam the target sits in and estimate its elevation from the amplitudes of that
+ * beam and its neighbours: rsp_beam_fuse_dev's d_famp / d_fflag go to rsp_condense_dev and
+ * rsp_motion_measure_dev as they stand (d_famp as both the sum and the difference plane), and
+ * rsp_beam_elev_dev writes the third estimate of that measurement, which rsp_track_dev reads.
+ *
+ * d_amp float32, d_flag uint8: `beams` planes per CPI, each V rows of R columns; cell (b, k, v, r) is
+ * element b*cpi_stride + k*beam_stride + v*ld + r.  The three strides serve [batch][beams][V][ld]
+ * (the defaults) and rsp_window_pc_mtd_cfar_dev's [beams][batch][V][R] (beam_stride = batch*V*R,
+ * cpi_stride = V*R).  Every output is dense [batch][V][R].
+ *
+ * rsp_beam_fuse_dev, per cell (b, v, r), with a_k the float32 amplitude of beam k and f_k its flag
+ * byte (any nonzero value is a hit):
+ *   cnt      the number of k with f_k != 0; the cell is a fused hit when cnt >= min_beams.
+ *   d_fcnt   uint8, nullable: cnt.
+ *   d_fflag  uint8: 1 at a fused hit, otherwise 0.
+ *   d_fbeam  uint8: at a fused hit the flagged beam with the largest amplitude, compared as float32
+ *            with `>` in beam order (the first of equal amplitudes wins); elsewhere 255.
+ *   d_famp   float32, nullable: m after m = a_0; for k = 1 ..: if (a_k > m) m = a_k -- over all beams,
+ *            flagged or not, at every cell.  With a NaN amplitude d_famp and d_fbeam are
+ *            unspecified, as the peak of rsp_condense_dev is.
+ * Every cell of every output is written once, by one thread; the caller clears nothing.  No atomics,
+ * no LDS, nothing combined across threads: two runs give the same bytes, and a CPI gives the same
+ * bytes alone as inside a batch.  A thread owns four consecutive columns of one row of one CPI and
+ * loads them with one 16-byte amplitude load (4-byte aligned) and one 4-byte flag load per beam; it
+ * takes its cells one by one where they run past the row end or where a flag or byte-output address
+ * of its four cells is not 4-byte aligned (odd R, ld, strides or bases).  Both ways give the same
+ * bytes.  One launch per 2^30 workgroups, asynchronous on `stream`; nothing is allocated or copied.
+ *
+ * rsp_beam_elev_dev, one thread per listed hit.  d_cells int32 [batch][max_hits][2] = (row, col) and
+ * d_count int32 [batch][2] are what rsp_motion_measure_dev writes, on d_famp with d_fflag or with a
+ * condensed peak plane.  Hit i < min(d_count[cpi*2], max_hits) of a CPI gets
+ * d_el[(cpi*max_hits + i) * el_stride] (float64; el_stride = 3 and d_el = d_est + 2 is the
+ * measurement's est[..][2]) and, with d_hb (int32 [batch][max_hits][4]), {peak beam k, flagged beams
+ * at the cell, lower beam used, upper beam used}; the last two are k-1 and k+1 where the elevation
+ * came from the three beams and -1, -1 where it is x_k or NaN, and the first is -1 where k is 255.
+ * Entries at or past that count are left untouched, as is everything between the d_el entries.
+ * With k = d_fbeam at the cell (read as 255 when it is >= beams, or when the cell lies outside
+ * V x R), x_i = beam_el[i] and the amplitudes widened to double:
+ *   1. k is 255: NaN.
+ *   2. law == 0, or k is the first or the last beam: x_k.
+ *   3. law == 1: w_i = a_i * a_i for i = k-1, k, k+1 (-, 0, +);
+ *      el = ((w_- x_- + w_0 x_0) + w_+ x_+) / ((w_- + w_0) + w_+); x_k where the denominator is zero
+ *      or not finite.
+ *   4. law == 2: x_k where any of the three amplitudes is <= 0 or not finite.  Otherwise
+ *      y_i = log(a_i), dm = x_0 - x_-, dp = x_0 - x_+, A = y_0 - y_+, B = y_0 - y_-,
+ *      den = dm*A - dp*B, xv = x_0 - 0.5 * (dm*dm*A - dp*dp*B) / den; x_k where
+ *      den * (x_+ - x_-) <= 0 (flat or convex) or xv is not finite; otherwise xv clamped to
+ *      [min(x_-, x_+), max(x_-, x_+)].
+ * For Gaussian beams of one width on any spacing log a is a parabola in the angle, and law 2 is exact
+ * up to rounding.  All fp64, contraction off, in exactly this order (csrc/rsp_fuse_math.h).
+ *
+ * Refused with RSP_ERR_ARG and a message, before the context is looked at: a NULL params, input or
+ * required output; beams outside 2..32, min_beams outside 1..beams, law outside 0..2, reserved != 0;
+ * a bad shape; ld < R; strides under which the address ranges ((V-1)*ld + R elements each) of two
+ * different (CPI, beam) planes overlap -- the beams of a CPI must lie inside its cpi_stride, or the
+ * CPIs of a beam inside its beam_stride; non-finite or not strictly monotonic centres; misaligned
+ * float, int or double pointers; an output of rsp_beam_fuse_dev that overlaps an input or another
+ * output; and for
+ * rsp_beam_elev_dev max_hits < 0, el_stride < 1 or more than 2^31 - 1 blocks of 256 hits.
+ * Both work on any context, the CFAR-only kind included. */
+#define RSP_FUSE_MAX_BEAMS 32
+typedef struct {
+    int32_t beams;          /* 2..32 */
+    int32_t min_beams;      /* 1..beams: flagged beams a cell needs to become a fused hit */
+    int32_t law;            /* 0 centre of the peak beam, 1 power centroid of three beams, 2 log-parabola */
+    int32_t reserved;       /* 0 */
+    int64_t ld;             /* row pitch of the input planes in elements (0 = R) */
+    int64_t beam_stride;    /* elements between the beams' planes of one CPI (0 = V*ld) */
+    int64_t cpi_stride;     /* elements between CPIs (0 = beams*V*ld) */
+    double  beam_el[32];    /* beam centres [deg], strictly monotonic over the first `beams` */
+} rsp_fuse_params;
+
+int rsp_beam_fuse_dev(rsp_ctx* ctx, const float* d_amp, const uint8_t* d_flag, int64_t V, int64_t R,
+                      int64_t batch, const rsp_fuse_params* fp, uint8_t* d_fflag, uint8_t* d_fbeam,
+                      float* d_famp /* nullable */, uint8_t* d_fcnt /* nullable */, void* stream);
+
+int rsp_beam_elev_dev(rsp_ctx* ctx, const float* d_amp, const uint8_t* d_flag, const uint8_t* d_fbeam,
+                      int64_t V, int64_t R, int64_t batch, const rsp_fuse_params* fp,
+                      const int32_t* d_cells /* [batch][max_hits][2], (row, col) */,
+                      const int32_t* d_count /* [batch][2] */, int64_t max_hits,
+                      double* d_el, int64_t el_stride, int32_t* d_hb /* nullable, [batch][max_hits][4] */,
+                      void* stream);
 
 /* ---- detection scoring against truth (main_cfar.m's evaluation functions) ---------------- */
 /* The four local functions at the end of MatlabProcess_xuzerui/CFAR_WangCai/main_cfar.m, the

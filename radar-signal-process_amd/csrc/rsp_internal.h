@@ -293,6 +293,22 @@ hipError_t launch_integ_sum(const float* in, float* hist, const int32_t* shift, 
 hipError_t launch_integ_bin(const uint8_t* in, uint8_t* hist, const int32_t* shift, const int32_t* slot, int32_t* meta,
                             int32_t* plan, uint8_t* out, int32_t* neff, int64_t batch, const IntegArgs& a, hipStream_t st);
 
+// Stacked-beam fusion (rsp_fuse.hip): rsp_fuse_params with the shape and the resolved strides.
+struct FuseArgs {
+    int V, R;
+    int beams, min_beams, law;
+    int64_t ld, bs, cs;    // row pitch, beam stride and CPI stride of the input planes, in elements
+    double beam_el[32];
+};
+// One streaming launch per 2^30 workgroups.  famp, fcnt may be null.
+hipError_t launch_beam_fuse(const float* amp, const uint8_t* flag, uint8_t* fflag, uint8_t* fbeam, float* famp,
+                            uint8_t* fcnt, int64_t batch, const FuseArgs& a, hipStream_t st);
+// One thread per slot of the hit lists; blocks of 256 slots per CPI.  hb may be null.
+int64_t beam_elev_blocks(int64_t batch, int64_t max_hits);
+hipError_t launch_beam_elev(const float* amp, const uint8_t* flag, const uint8_t* fbeam, const int32_t* cells,
+                            const int32_t* count, int64_t max_hits, double* el, int64_t el_stride, int32_t* hb,
+                            int64_t batch, const FuseArgs& a, hipStream_t st);
+
 // Detection scoring (rsp_score.hip): rsp_score_params with the shape and the resolved pitches.
 struct ScoreArgs {
     int V, R;

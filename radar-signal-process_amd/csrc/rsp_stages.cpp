@@ -1,8 +1,8 @@
 // rsp_stages.cpp -- the C ABI's stage entry points around the chain (include/rsp.h): post-detection
 // measurement, plot condensation, clutter map, Doppler line width, detection scoring, echo pre-filters, target
-// injection, raw-data ingest, the legacy record ingest, tracking and post-detection integration.  Each
-// validates its arguments and launches its stage's kernels (rsp_<stage>.hip); the context, the presets
-// and the PC -> MTD -> CFAR chain are in rsp_capi.cpp.
+// injection, raw-data ingest, the legacy record ingest, tracking, post-detection integration and the fusion
+// of stacked beams.  Each validates its arguments and launches its stage's kernels (rsp_<stage>.hip); the
+// context, the presets and the PC -> MTD -> CFAR chain are in rsp_capi.cpp.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -892,4 +892,109 @@ int rsp_binint_dev(rsp_ctx* ctx, const uint8_t* d_in, int64_t V, int64_t R, int6
     if ((rc = integ_pool(ctx, batch, a.n, st, &plan))) return rc;
     HIP_TRY(ctx, rsp::launch_integ_bin(d_in, d_hist, d_shift, d_slot, d_meta, plan, d_out, d_neff, batch, a, st));
     return scratch_release(ctx, st);
+}
+
+// ------------------------------------------------------------------ stacked beams: fusion and elevation
+// What both calls check about the shape, the parameters and the input planes, before the context is looked at.
+static int fuse_check(rsp_ctx* ctx, const char* who, const float* d_amp, const uint8_t* d_flag, int64_t V, int64_t R,
+                      int64_t batch, const rsp_fuse_params* fp, rsp::FuseArgs* a, int64_t* extent) {
+    if (!fp || !d_amp || !d_flag)
+        return fail(ctx, RSP_ERR_ARG, "%s: null %s", who, !fp ? "params" : !d_amp ? "d_amp" : "d_flag");
+    if (V < 1 || R < 1 || V > (1 << 20) || R > (1 << 20) || V * R > (int64_t)1 << 31 || batch < 0 || batch > 0x7fffffff)
+        return fail(ctx, RSP_ERR_ARG, "%s: bad shape %lld x %lld x %lld", who, (long long)batch, (long long)V, (long long)R);
+    if (fp->beams < 2 || fp->beams > RSP_FUSE_MAX_BEAMS)
+        return fail(ctx, RSP_ERR_ARG, "%s: beams = %d outside 2..%d", who, fp->beams, RSP_FUSE_MAX_BEAMS);
+    if (fp->min_beams < 1 || fp->min_beams > fp->beams)
+        return fail(ctx, RSP_ERR_ARG, "%s: min_beams = %d outside 1..beams = %d", who, fp->min_beams, fp->beams);
+    if (fp->law < 0 || fp->law > 2) return fail(ctx, RSP_ERR_ARG, "%s: law = %d outside 0..2", who, fp->law);
+    if (fp->reserved != 0) return fail(ctx, RSP_ERR_ARG, "%s: reserved = %d", who, fp->reserved);
+    const int64_t beams = fp->beams;
+    const int64_t ld = fp->ld ? fp->ld : R;
+    if (ld < R || ld > ((int64_t)1 << 40))
+        return fail(ctx, RSP_ERR_ARG, "%s: row pitch %lld for %lld columns", who, (long long)ld, (long long)R);
+    const int64_t plane = (V - 1) * ld + R;   // the address range of one (CPI, beam) plane, in elements
+    const int64_t bs = fp->beam_stride ? fp->beam_stride : V * ld;
+    const int64_t cs = fp->cpi_stride ? fp->cpi_stride : beams * V * ld;
+    const int64_t lim = (int64_t)1 << 56;
+    bool ok = bs >= plane && bs <= lim / beams && (batch < 2 || (cs >= plane && cs <= lim / batch));
+    if (ok && batch > 1) {
+        const bool beam_inside = cs >= (beams - 1) * bs + plane;   // [batch][beams][V][ld]
+        const bool cpi_inside = bs >= (batch - 1) * cs + plane;    // [beams][batch][V][ld]
+        ok = beam_inside || cpi_inside;
+    }
+    if (!ok)
+        return fail(ctx, RSP_ERR_ARG, "%s: beam stride %lld / CPI stride %lld: planes of %lld elements overlap (%lld beams, %lld CPIs)",
+                    who, (long long)bs, (long long)cs, (long long)plane, (long long)beams, (long long)batch);
+    for (int k = 0; k < fp->beams; ++k)
+        if (!std::isfinite(fp->beam_el[k])) return fail(ctx, RSP_ERR_ARG, "%s: beam_el[%d] is not finite", who, k);
+    const bool up = fp->beam_el[1] > fp->beam_el[0];
+    for (int k = 1; k < fp->beams; ++k)
+        if (up ? !(fp->beam_el[k] > fp->beam_el[k - 1]) : !(fp->beam_el[k] < fp->beam_el[k - 1]))
+            return fail(ctx, RSP_ERR_ARG, "%s: beam_el is not strictly monotonic at %d", who, k);
+    if ((uintptr_t)d_amp & 3) return fail(ctx, RSP_ERR_ARG, "%s: misaligned d_amp (floats: 4 bytes)", who);
+    a->V = (int)V;
+    a->R = (int)R;
+    a->beams = fp->beams;
+    a->min_beams = fp->min_beams;
+    a->law = fp->law;
+    a->ld = ld;
+    a->bs = bs;
+    a->cs = cs;
+    for (int k = 0; k < RSP_FUSE_MAX_BEAMS; ++k) a->beam_el[k] = k < fp->beams ? fp->beam_el[k] : 0.0;
+    *extent = batch > 0 ? (batch - 1) * cs + (beams - 1) * bs + plane : 0;   // elements from the base to the last cell
+    return RSP_OK;
+}
+
+int rsp_beam_fuse_dev(rsp_ctx* ctx, const float* d_amp, const uint8_t* d_flag, int64_t V, int64_t R, int64_t batch,
+                      const rsp_fuse_params* fp, uint8_t* d_fflag, uint8_t* d_fbeam, float* d_famp, uint8_t* d_fcnt,
+                      void* stream) {
+    const char* who = "rsp_beam_fuse_dev";
+    rsp::FuseArgs a{};
+    int64_t extent = 0;
+    int rc = fuse_check(ctx, who, d_amp, d_flag, V, R, batch, fp, &a, &extent);
+    if (rc) return rc;
+    if (!d_fflag || !d_fbeam) return fail(ctx, RSP_ERR_ARG, "%s: null %s", who, !d_fflag ? "d_fflag" : "d_fbeam");
+    if ((uintptr_t)d_famp & 3) return fail(ctx, RSP_ERR_ARG, "%s: misaligned d_famp (floats: 4 bytes)", who);
+    const int64_t cells = batch * V * R;
+    struct { const void* p; int64_t n; const char* name; } outs[] = {
+        {d_fflag, cells, "d_fflag"}, {d_fbeam, cells, "d_fbeam"}, {d_famp, cells * 4, "d_famp"}, {d_fcnt, cells, "d_fcnt"}};
+    for (int i = 0; i < 4 && cells > 0; ++i) {
+        if (!outs[i].p) continue;
+        if (ranges_overlap(outs[i].p, outs[i].n, d_amp, extent * 4) || ranges_overlap(outs[i].p, outs[i].n, d_flag, extent))
+            return fail(ctx, RSP_ERR_ARG, "%s: %s overlaps an input", who, outs[i].name);
+        for (int j = 0; j < i; ++j)
+            if (outs[j].p && ranges_overlap(outs[i].p, outs[i].n, outs[j].p, outs[j].n))
+                return fail(ctx, RSP_ERR_ARG, "%s: %s overlaps %s", who, outs[i].name, outs[j].name);
+    }
+    if (!ctx) return fail(nullptr, RSP_ERR_ARG, "%s: null ctx", who);
+    if (batch == 0) return RSP_OK;
+    if (!set_device(ctx)) return fail(ctx, RSP_ERR_HIP, "hipSetDevice failed");
+    HIP_TRY(ctx, rsp::launch_beam_fuse(d_amp, d_flag, d_fflag, d_fbeam, d_famp, d_fcnt, batch, a, (hipStream_t)stream));
+    return RSP_OK;
+}
+
+int rsp_beam_elev_dev(rsp_ctx* ctx, const float* d_amp, const uint8_t* d_flag, const uint8_t* d_fbeam, int64_t V, int64_t R,
+                      int64_t batch, const rsp_fuse_params* fp, const int32_t* d_cells, const int32_t* d_count,
+                      int64_t max_hits, double* d_el, int64_t el_stride, int32_t* d_hb, void* stream) {
+    const char* who = "rsp_beam_elev_dev";
+    rsp::FuseArgs a{};
+    int64_t extent = 0;
+    int rc = fuse_check(ctx, who, d_amp, d_flag, V, R, batch, fp, &a, &extent);
+    if (rc) return rc;
+    if (!d_fbeam || !d_count) return fail(ctx, RSP_ERR_ARG, "%s: null %s", who, !d_fbeam ? "d_fbeam" : "d_count");
+    if (max_hits < 0 || max_hits > 0x7fffffff || el_stride < 1 || el_stride > (1 << 20))
+        return fail(ctx, RSP_ERR_ARG, "%s: max_hits = %lld, el_stride = %lld", who, (long long)max_hits, (long long)el_stride);
+    if (max_hits > 0 && (!d_cells || !d_el)) return fail(ctx, RSP_ERR_ARG, "%s: null %s", who, !d_cells ? "d_cells" : "d_el");
+    if (rsp::beam_elev_blocks(batch, max_hits) > 0x7fffffff)
+        return fail(ctx, RSP_ERR_ARG, "%s: %lld CPIs of %lld hits are more than 2^31 - 1 blocks of 256", who, (long long)batch,
+                    (long long)max_hits);
+    if (((uintptr_t)d_cells | (uintptr_t)d_count | (uintptr_t)d_hb) & 3)
+        return fail(ctx, RSP_ERR_ARG, "%s: misaligned argument (ints: 4 bytes)", who);
+    if ((uintptr_t)d_el & 7) return fail(ctx, RSP_ERR_ARG, "%s: misaligned d_el (doubles: 8 bytes)", who);
+    if (!ctx) return fail(nullptr, RSP_ERR_ARG, "%s: null ctx", who);
+    if (batch == 0 || max_hits == 0) return RSP_OK;
+    if (!set_device(ctx)) return fail(ctx, RSP_ERR_HIP, "hipSetDevice failed");
+    HIP_TRY(ctx, rsp::launch_beam_elev(d_amp, d_flag, d_fbeam, d_cells, d_count, max_hits, d_el, el_stride, d_hb, batch, a,
+                                       (hipStream_t)stream));
+    return RSP_OK;
 }

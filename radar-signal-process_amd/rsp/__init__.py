@@ -11,10 +11,13 @@ rsp.width measures how wide the Doppler line of a detection's range column stand
 measurement, rsp.track joins the estimates of successive CPIs into tracks.  rsp.oscfar is a second
 detector beside the chain's cell-averaging CFAR: the ordered-statistic one.  rsp.integrate sums or
 counts the planes of the last CPIs of a dwell, range walk compensated, around either detector.
+rsp.fuse merges the hits of the v2 capture's stacked elevation beams per cell and estimates the
+elevation from the beam amplitudes, which takes that stream to the measurement and the tracker.
 """
-from . import _capi, cmap, integrate, oscfar, presets, synth, track, width  # noqa: F401
+from . import _capi, cmap, fuse, integrate, oscfar, presets, synth, track, width  # noqa: F401
 from ._capi import RspError, load_library  # noqa: F401
 from .cmap import ClutterMap, band_of  # noqa: F401
+from .fuse import BeamFuser  # noqa: F401
 from .integrate import Integrator, walk_shifts  # noqa: F401
 from .oscfar import OsCfar  # noqa: F401
 from .track import Tracker  # noqa: F401

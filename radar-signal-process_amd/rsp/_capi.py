@@ -35,7 +35,8 @@ EXPORTS = ("rsp_version", "rsp_create", "rsp_destroy", "rsp_last_error", "rsp_se
            "rsp_set_pc_prune", "rsp_set_lane_chunks", "rsp_pc_plan", "rsp_scr_dev", "rsp_inject_dev", "rsp_scr_gain",
            "rsp_cfar_plan", "rsp_legacy_record_bytes", "rsp_ingest_legacy_dev", "rsp_condense_dev", "rsp_cmap_dev",
            "rsp_cmap_plan", "rsp_spec_width_dev", "rsp_track_dev", "rsp_set_pc_rows", "rsp_get_pc_rows",
-           "rsp_os_cfar_dev", "rsp_os_cfar_plan", "rsp_measure_plan", "rsp_integrate_dev", "rsp_binint_dev")
+           "rsp_os_cfar_dev", "rsp_os_cfar_plan", "rsp_measure_plan", "rsp_integrate_dev", "rsp_binint_dev",
+           "rsp_beam_fuse_dev", "rsp_beam_elev_dev")
 RSP_NKERNELS = 6
 KERNEL_NAMES = ("pc_kernel", "mtd_kernel", "cfar_r_kernel", "cfar_v_kernel", "os_v_kernel", "os_r_kernel")
 
@@ -160,6 +161,15 @@ RSP_INTEG_MAX_N = 16
 class rsp_integ_params(C.Structure):
     _fields_ = [("n", C.c_int32), ("m", C.c_int32), ("spread", C.c_int32), ("reserved", C.c_int32),
                 ("ld", C.c_int64), ("cpi_stride", C.c_int64)]
+
+
+RSP_FUSE_MAX_BEAMS = 32
+
+
+class rsp_fuse_params(C.Structure):
+    _fields_ = [("beams", C.c_int32), ("min_beams", C.c_int32), ("law", C.c_int32), ("reserved", C.c_int32),
+                ("ld", C.c_int64), ("beam_stride", C.c_int64), ("cpi_stride", C.c_int64),
+                ("beam_el", C.c_double * RSP_FUSE_MAX_BEAMS)]
 
 
 class rsp_score_params(C.Structure):
@@ -322,6 +332,11 @@ def load_library(path=None):
     for fn in (lib.rsp_integrate_dev, lib.rsp_binint_dev):
         fn.restype = C.c_int
         fn.argtypes = [vp, vp, i64, i64, i64, C.POINTER(rsp_integ_params), vp, vp, i32, vp, vp, vp, vp, vp]
+    lib.rsp_beam_fuse_dev.restype = C.c_int
+    lib.rsp_beam_fuse_dev.argtypes = [vp, vp, vp, i64, i64, i64, C.POINTER(rsp_fuse_params), vp, vp, vp, vp, vp]
+    lib.rsp_beam_elev_dev.restype = C.c_int
+    lib.rsp_beam_elev_dev.argtypes = [vp, vp, vp, vp, i64, i64, i64, C.POINTER(rsp_fuse_params), vp, vp, i64, vp, i64,
+                                      vp, vp]
     lib.rsp_score_dev.restype = C.c_int
     lib.rsp_score_dev.argtypes = [vp, vp, vp, i64, i64, i64, C.POINTER(rsp_score_params), vp, vp, vp]
     lib.rsp_score_summary.restype = C.c_int
